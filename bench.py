@@ -9,6 +9,10 @@ resident in HBM before the timed region.  Default workload: configs[1] of BASELI
 B = 4096 four-contact stance states, cold solves, per GPU (weak scaling).
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under torch.distributed.run.
+That plain run sets up, warms up, times the K steps and prints the result line (--dump-outputs DIR
+also writes the last timed step's outputs as .npy).  --full adds, after the timed steps, the
+kernel's duration and the rooflines, the CPU baseline and, with --extra / --breakdown, the other
+configurations and forms of the step.
 """
 import argparse
 import json
@@ -240,7 +244,7 @@ def make_engine(cfg, B, seed, device, stream):
     return e, (e.step_modes if K else e.step), inp
 
 
-def bench_trot(torch, stream, device, STATELESS, B=4096, T=400, seed=2):
+def bench_trot(torch, stream, device, STATELESS, B=4096, T=400, seed=2, dump=None):
     """BASELINE configs[2]: B robots trotting for T cycles (1 s at 400 Hz), alternating 2-contact
     modes, history carried across steps (stateful path: finite differences, Tdot_inv lag, integral
     error).  All T steps of inputs are staged in HBM first and bound per step (no copies timed)."""
@@ -275,6 +279,8 @@ def bench_trot(torch, stream, device, STATELESS, B=4096, T=400, seed=2):
     ms = ev0.elapsed_time(ev1)
     o = e.outputs()
     e.close()
+    if dump:  # the last step's outputs (no x: the steps run with WBC_NO_X)
+        dump_outputs(dump, tau=o["tau"], grf=o["grf"], status=o["status"], iters=o["iters"])
     its = np.stack(its)
     tr, tr_src = committed_traffic("trot_stateful_b4096", B)
     rl = roofline_of(step_flops(B * T, its) / T, ms / T, tr.get("step"), tr_src)
@@ -344,6 +350,24 @@ def shard_inputs(cfg, scaling, world, rank):
     return S_rank * (K or 1), S_rank, inp, modes, S_tot * (K or 1)
 
 
+def dump_outputs(path, limit=52 << 20, **arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64 (status and iters are small integers,
+    exact in it).  The configs' outputs are at most 27 MB; of a batch whose outputs pass `limit` (52 MB,
+    so that at most 64 MB are written with the row numbers) the same seeded sample of rows (robots) is
+    written every run, with its row numbers as rows_<name>.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > limit:
+        for k in list(arrays):
+            n = len(arrays[k])
+            rows = np.sort(np.random.default_rng(0).choice(n, size=n * limit // nbytes, replace=False))
+            arrays[k] = np.ascontiguousarray(arrays[k][rows])
+            arrays["rows_" + k] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -356,11 +380,24 @@ def main():
                     help="weak: the config's batch per GPU; strong: the config's batch in total, sharded "
                          "(default: the config's own)")
     ap.add_argument("--batch", type=int, default=0, help="override the config's batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take what the headline figure does not need: the kernel's "
+                         "duration and the rooflines (a second run of --steps steps under HIP events) and the CPU "
+                         "baseline; --extra and --breakdown add to it.  Without it the run sets up, warms up, times "
+                         "the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step, as the step loop's caller holds them, to "
+                         "DIR/<name>.npy (float64): tau [B, 12], status [B], iters [B] of the whole batch and "
+                         "grf [B, 12] (N > 1: grf_rank0, rank 0's rows, which the gather leaves out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--extra", action="store_true", help="also time the other configs (reported under 'extra')")
-    ap.add_argument("--breakdown", action="store_true", help="also time the update and solve kernels separately")
+    ap.add_argument("--extra", action="store_true",
+                    help="also time the other configs (reported under 'extra'); implies --full")
+    ap.add_argument("--breakdown", action="store_true",
+                    help="also time the update and solve kernels separately; implies --full")
     args = ap.parse_args()
+    if args.extra or args.breakdown:
+        args.full = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))
@@ -396,7 +433,7 @@ def main():
             sys.exit(2)
         stream = torch.cuda.Stream()
         torch.cuda.set_stream(stream)
-        r = bench_trot(torch, stream, local_rank, STATELESS)
+        r = bench_trot(torch, stream, local_rank, STATELESS, dump=args.dump_outputs)
         print(json.dumps(dict(metric="WBC QP solves/sec, configs[2] trot (stateful)", value=r["solves_per_s"],
                               unit="solves/s", n_gpus=1, config={"workload": args.config}, trot=r)), flush=True)
         return
@@ -451,7 +488,52 @@ def main():
     # whole-batch outputs of the last timed step, as every rank holds them after the gather
     g_tau, g_status, g_iters = pipe.result(pipe.last_slot, (B * world if scaling == "weak" else B_total)
                                            if world > 1 else B, unit=K or 1)
+    # this rank's outputs of that step (tau, status, iters out of its block; grf, which the gather
+    # leaves out, from the engine's own buffer)
+    out = e.outputs()
+    iters = out["iters"].astype(np.int64)
+    status = out["status"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tau=g_tau, status=g_status, iters=g_iters,
+                     **{"grf" if world == 1 else "grf_rank0": out["grf"]})
     pipe.bind(0)
+
+    total = (B * world if scaling == "weak" else B_total) * args.steps
+    value = total / elapsed
+    result = {
+        "metric": "WBC QP solves/sec (ANYmal 18-DoF, 4-contact) at 1/2/4/8 GPUs; % HBM roofline",
+        "value": value,
+        "unit": "solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SURVEY.md 8d generators, numpy PCG64 seed %d%s)"
+                % (cfg["seed"], " + 1000*rank" if scaling == "weak" else ", global batch sharded by rank"),
+        "config": {"workload": args.config, "description": cfg["desc"], "batch_per_gpu": B,
+                   "global_batch": B * world if scaling == "weak" else B_total,
+                   "parallelism": f"dp{world}" + (" (robot shards; RCCL all-gather of tau|status|iters per step, "
+                                                  "overlapped with the next step)" if world > 1 else "")},
+        "qp_status_counts": np.bincount(status, minlength=4).tolist(),
+        "mean_iters": float(iters.mean()),
+        "gathered": {"robots": int(len(g_status)), "status_counts": np.bincount(g_status, minlength=4).tolist(),
+                     "mean_iters": float(np.mean(g_iters)), "tau_abs_sum": float(np.abs(g_tau).sum())},
+    }
+
+    def finish():
+        e.close()
+        if world > 1:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+
+    if not args.full:  # the plain run ends here: the headline figure needs nothing below
+        finish()
+        return
 
     # Kernel duration for the roofline: HIP events on the launch stream around K back-to-back
     # launches (this includes the few-us dispatch gap between launches, which rocprofv3's
@@ -470,9 +552,6 @@ def main():
     # the rare unusable reduction solved there too by the general method): the step's time is that
     # kernel's.  It owns all of SURVEY 8(d)'s flops.
     step_ms = timed(lambda: step(STEP_FLAGS))
-    out = e.outputs()
-    iters = out["iters"].astype(np.int64)
-    status = out["status"]
     dom, dom_ms = step_kernel(e), step_ms
     kernels = {dom: step_ms}
     flops_step = step_flops(S, iters)
@@ -511,26 +590,7 @@ def main():
 
     traffic, traffic_src = committed_traffic(args.config, B)
     pmc_rec, _ = committed_pmc(args.config, B)
-    total = (B * world if scaling == "weak" else B_total) * args.steps
-    value = total / elapsed
-    result = {
-        "metric": "WBC QP solves/sec (ANYmal 18-DoF, 4-contact) at 1/2/4/8 GPUs; % HBM roofline",
-        "value": value,
-        "unit": "solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (SURVEY.md 8d generators, numpy PCG64 seed %d%s)"
-                % (cfg["seed"], " + 1000*rank" if scaling == "weak" else ", global batch sharded by rank"),
-        "config": {"workload": args.config, "description": cfg["desc"], "batch_per_gpu": B,
-                   "global_batch": B * world if scaling == "weak" else B_total,
-                   "parallelism": f"dp{world}" + (" (robot shards; RCCL all-gather of tau|status|iters per step, "
-                                                  "overlapped with the next step)" if world > 1 else "")},
+    result.update({
         "roofline": {"bound": "fp64_valu", "achieved": tf_dom, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": tf_dom / FP64_PEAK_TFLOPS, "traffic": traffic.get(dom),
                      "traffic_source": traffic_src, "kernel": dom, "kernel_ms": dom_ms,
@@ -551,11 +611,7 @@ def main():
                          "note": "algorithmic bytes over the step (all its kernels): 729 B read per state + 200 B "
                                  "written per QP (929 B/solve one QP per state); traffic = PMC bytes per step "
                                  "(all its kernels, incl. any problem hand-off between them)"},
-        "qp_status_counts": np.bincount(status, minlength=4).tolist(),
-        "mean_iters": float(iters.mean()),
-        "gathered": {"robots": int(len(g_status)), "status_counts": np.bincount(g_status, minlength=4).tolist(),
-                     "mean_iters": float(np.mean(g_iters)), "tau_abs_sum": float(np.abs(g_tau).sum())},
-    }
+    })
     if extra:
         result["extra"] = extra
     if breakdown:
@@ -567,11 +623,7 @@ def main():
         result["cpu_baseline"]["host"] = dict(nproc=multiprocessing.cpu_count(), model=_cpu_model())
     elif world > 1:
         result["cpu_baseline_note"] = "timed at N=1 only (rank 0), per the bench contract"
-    e.close()
-    if world > 1:
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
+    finish()
 
 
 def _cpu_model():

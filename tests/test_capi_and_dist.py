@@ -147,9 +147,19 @@ for B, unit in ((67, 1), (5 * 4, 4)):
         full = wbc_ref.run_batch(inp, max_torque=20.0)
         assert np.array_equal(tau, full["tau"]), "gathered torques differ"
         assert np.array_equal(st, full["status"]) and np.array_equal(it, full["iters"])
-print("DIST_OK", rank)
+print("DIST_OK", rank, flush=True)
 dist.destroy_process_group()
 """
+
+
+def _free_port():
+    """A port nobody listens on now (as bench._self_launch picks one): a fixed port fails with
+    EADDRINUSE when another run of this suite on the same host holds it."""
+    import socket
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
 
 
 @pytest.mark.parametrize("world", [2, 4])
@@ -160,10 +170,10 @@ def test_two_rank_gloo_shard_and_gather(tmp_path, world):
     script.write_text(DIST_WORKER.format(root=ROOT))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-           "--master-addr=127.0.0.1", f"--master-port={29531 + world}", str(script)]
+           "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(script)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert all(f"DIST_OK {k}" in r.stdout for k in range(world))
+    assert all(f"DIST_OK {k}" in r.stdout for k in range(world)), (r.stdout[-2000:], r.stderr[-2000:])
 
 
 def test_bench_world_mismatch_exits_nonzero():

@@ -62,12 +62,22 @@ dist.destroy_process_group()
 """
 
 
+def _free_port():
+    """A port nobody listens on now (as bench._self_launch picks one): a fixed port fails with
+    EADDRINUSE when another run of this suite on the same host holds it."""
+    import socket
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 def test_two_rank_engine_shards_gather_to_the_full_batch(tmp_path):
     script = tmp_path / "worker.py"
     script.write_text(WORKER.format(root=ROOT))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr=127.0.0.1", "--master-port=29533", str(script)]
+           "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(script)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     assert "DIST_OK 0" in r.stdout and "DIST_OK 1" in r.stdout

@@ -96,13 +96,23 @@ dist.destroy_process_group()
 """
 
 
+def _free_port():
+    """A port nobody listens on now (as bench._self_launch picks one): a fixed port fails with
+    EADDRINUSE when another run of this suite on the same host holds it."""
+    import socket
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 def test_rccl_gather_and_step_pipeline_on_one_rank(tmp_path):
     script = tmp_path / "worker.py"
     script.write_text(WORKER.format(root=ROOT))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
-           "--master-addr=127.0.0.1", "--master-port=29547", str(script)]
+           "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(script)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     assert "GATHER_OK" in r.stdout and "PIPE_OK" in r.stdout

@@ -1,7 +1,9 @@
 """CPU: wbc_model_from_urdf (C++ run-time URDF loader) against the Python
 generator tools/gen_model.py on synthetic quadruped URDFs (different names, extra fixed links,
 rotated joint frames, off-axis inertials), against the committed ANYmal constants when the
-reference URDF is present in this container, and its error paths.
+reference URDF is present in this container, and its error paths.  The committed constants are also
+checked without it: the JSON and the C header hold the same numbers, and a URDF written from the
+committed lumped model loads back to them.
 """
 import ctypes as C
 import os
@@ -92,10 +94,63 @@ def test_loader_matches_python_generator(tmp_path, seed):
     assert np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))) < 1e-13
 
 
+def lumped_urdf(path, d):
+    """The 13-body model of model/anymal.json (tools/gen_model.py's output) written back as a URDF:
+    base, three revolute links per leg at the stored joint frames, a massless fixed foot frame."""
+    def inertial(b):
+        I = b["inertia"]
+        return (f'<inertial><origin xyz="{_f(b["com"])}" rpy="0 0 0"/><mass value="{float(b["mass"])!r}"/>'
+                f'<inertia ixx="{I[0][0]!r}" ixy="{I[0][1]!r}" ixz="{I[0][2]!r}" iyy="{I[1][1]!r}" '
+                f'iyz="{I[1][2]!r}" izz="{I[2][2]!r}"/></inertial>')
+
+    def rpy(R):  # inverse of R = Rz(yaw) Ry(pitch) Rx(roll)
+        return [np.arctan2(R[2][1], R[2][2]), -np.arcsin(R[2][0]), np.arctan2(R[1][0], R[0][0])]
+
+    out = ['<?xml version="1.0"?>', '<robot name="lumped">', f'<link name="base">{inertial(d["base"])}</link>']
+    for leg, links, foot, foot_name in zip(d["leg_order"], d["legs"], d["foot"], d["foot_names"]):
+        parent = "base"
+        for lk in links:
+            out.append(f'<link name="{lk["body"]}">{inertial(lk)}</link>')
+            out.append(f'<joint name="{lk["joint"]}" type="revolute"><parent link="{parent}"/>'
+                       f'<child link="{lk["body"]}"/><origin xyz="{_f(lk["p"])}" rpy="{_f(rpy(lk["R"]))}"/>'
+                       f'<axis xyz="{_f(lk["axis"])}"/></joint>')
+            parent = lk["body"]
+        out.append(f'<link name="{foot_name}"/>')
+        out.append(f'<joint name="{foot_name}_joint" type="fixed"><parent link="{parent}"/>'
+                   f'<child link="{foot_name}"/><origin xyz="{_f(foot)}"/></joint>')
+    out.append("</robot>")
+    with open(path, "w") as fh:
+        fh.write("\n".join(out))
+
+
 def test_loader_reproduces_committed_anymal_model():
     if not os.path.exists(REF_URDF):
         pytest.skip("reference URDF not in this container")
     assert np.array_equal(model_array(model_from_urdf(REF_URDF)), model_array(anymal_model()))
+
+
+def committed_lumped_model():
+    import json
+
+    with open(os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "model", "anymal.json")) as fh:
+        return json.load(fh)
+
+
+def test_committed_json_and_header_hold_the_same_model():
+    """model/anymal.json and include/wbc_anymal_model.h (what anymal_model() returns), both written by
+    tools/gen_model.py with repr(), hold the same doubles."""
+    assert np.array_equal(python_model_array(committed_lumped_model()), model_array(anymal_model()))
+
+
+def test_loader_round_trips_committed_lumped_model(tmp_path):
+    """The committed ANYmal constants come back from the loader, with its default ANYmal names, on a
+    URDF of the committed lumped model.  The joint frames go through rpy angles and the massless foot
+    frames through the lumping sum, a few roundings each: the bound of the generator comparison above."""
+    p = str(tmp_path / "anymal_lumped.urdf")
+    lumped_urdf(p, committed_lumped_model())
+    a, b = model_array(model_from_urdf(p)), model_array(anymal_model())
+    assert a.shape == b.shape
+    assert np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))) < 1e-13
 
 
 def test_loader_errors(tmp_path):

@@ -1,6 +1,6 @@
 # Round evidence on one GPU box: GPU tests, smoke, PMC passes for the bench workloads (separate
 # runs; their summaries under profiles/$ROUND/ are what bench.py reads for roofline.traffic), the
-# default bench line (with the CPU baseline), the --extra configs, and a rocprofv3 kernel-trace
+# full bench line (--full: rooflines and the CPU baseline), the --extra configs, and a rocprofv3 kernel-trace
 # summary of the same bench command.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
@@ -24,8 +24,8 @@ for cb in stance_cold_b4096:4096 rl_random_b8192:8192 modes16_b16384:16384 trot_
 done
 fi
 if [ $PART = 1 ]; then echo part1 done; exit 0; fi
-step bench 300 python bench.py --steps 50 --warmup 5
-step bench_extra 300 python bench.py --steps 20 --warmup 3 --extra --breakdown --no-cpu-baseline
+step bench 300 python bench.py --full --steps 50 --warmup 5
+step bench_extra 300 python bench.py --full --steps 20 --warmup 3 --extra --breakdown --no-cpu-baseline
 step prof 300 rocprofv3 --kernel-trace --stats -d $O/prof -o prof --output-format csv -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline
 for cb in rl_random_b8192 modes16_b16384; do
   step prof_$cb 300 rocprofv3 --kernel-trace --stats -d $O/prof_$cb -o prof --output-format csv -- python3 bench.py --config $cb --steps 200 --warmup 20 --no-cpu-baseline

@@ -26,8 +26,8 @@ PY
             (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/qmap_prof -o run -- python3 $GRAFT_REPO_ROOT/tools/qmap_probe.py 10 > $GRAFT_REPO_ROOT/$O/qmap_prof.log 2>&1); rc=$?
           fi ;;
     calib) OUT=$O/calib bash tools/calib.sh > $O/calib.log 2>&1; rc=$?; tail -40 $O/calib.log ;;
-    bench) timeout -k 10 400 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 > $O/bench.log 2>&1; rc=$?; tail -1 $O/bench.log ;;
-    extra) timeout -k 10 400 python bench.py --steps 20 --warmup 3 --extra --no-cpu-baseline > $O/bench_extra.log 2>&1; rc=$?; grep '^{' $O/bench_extra.log | cut -c1-200 ;;
+    bench) timeout -k 10 400 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 > $O/bench.log 2>&1; rc=$?; tail -1 $O/bench.log ;;
+    extra) timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --extra --no-cpu-baseline > $O/bench_extra.log 2>&1; rc=$?; grep '^{' $O/bench_extra.log | cut -c1-200 ;;
     ust) for c in ${UST_CFGS:-stance_cold trot rl_random}; do
            B=4096; [ $c = rl_random ] && B=8192
            WBC_LIB=quadrupedwholebodycontroller_amd/libwbc_hip_istamps.so timeout -k 10 200 python tools/ust16.py $c $B > $O/ust_$c.log 2>&1; rc=$?
