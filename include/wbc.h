@@ -246,6 +246,49 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags);
  * it with a divisor of n_modes).  Results are bit-identical either way. */
 int32_t wbc_modes_per_wave(wbc_engine* h, int32_t* m);
 
+/* Per-robot controller parameters (an RL batch with randomised friction, actuator limit and gains;
+ * a sweep over gains): a table of doubles, row-major [B][WBC_RP_LEN], row b for robot b.  Rows are
+ * 80 bytes, so a table that starts 16-byte aligned keeps every row 16-byte aligned (required of a
+ * device-bound table).  While a table is in force the default wbc_step reads the nine values of
+ * each robot's QP from its row instead of the engine-wide wbc_params; loop_rate, gravity, max_wsr
+ * and initial_reference_pose stay engine-wide.  A robot's result depends only on its own row. */
+enum {
+    WBC_RP_FRICTION = 0,     /* wbc_params::friction */
+    WBC_RP_MAX_TORQUE = 1,   /* max_torque */
+    WBC_RP_KP = 2,           /* kp */
+    WBC_RP_KP_Z = 3,         /* kp_z */
+    WBC_RP_KD = 4,           /* kd */
+    WBC_RP_KI = 5,           /* ki */
+    WBC_RP_KP_SWING = 6,     /* kp_swing */
+    WBC_RP_KD_SWING = 7,     /* kd_swing */
+    WBC_RP_SLACK_WEIGHT = 8, /* slack_weight */
+    /* 9: reserved (ignored on input, written as 0 by wbc_get_robot_params) */
+    WBC_RP_LEN = 10
+};
+/* Host table, validated and then copied on the engine stream (the call synchronizes it, so the
+ * caller may reuse the array).  A non-finite entry in columns 0-8, friction < 0, max_torque < 0 or
+ * slack_weight <= 0 returns WBC_ERR_ARG, wbc_last_error names the row and the column, and the table
+ * in force before the call stays in force.  NULL clears the table: back to the engine-wide
+ * wbc_params.
+ * While a table is in force (this one or a device-bound one):
+ *  - supported: wbc_step in its default form (stateless, stateful and WBC_COLD; with WBC_DEBUG,
+ *    WBC_NO_X, WBC_TIMED and WBC_GROUP) and plain wbc_cycle.  A robot's row may change between
+ *    stateful cycles; history and hotstart carry over as they do when the inputs change.
+ *  - refused with WBC_ERR_STATE (wbc_last_error names the call or flag): wbc_update, wbc_solve,
+ *    wbc_step_modes, and wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT.  These
+ *    forms read the engine-wide parameters only; they run as before once the table is cleared
+ *    (wbc_set_robot_params(h, NULL) and no device table bound). */
+int32_t wbc_set_robot_params(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_RP_LEN] (no copy, no host validation; as
+ * wbc_bind_device_inputs: the step reads the pointer directly).  NULL restores the engine-owned
+ * table of wbc_set_robot_params, or none if none was set.  On the device a row that fails the
+ * predicate above gives that robot WBC_QP_NUMERIC and zero outputs, as a non-finite input does; no
+ * other robot is touched. */
+int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_RP_LEN] to the host (synchronous); without a table, the engine-wide
+ * values broadcast to B rows.  Column 9 is written as 0. */
+int32_t wbc_get_robot_params(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

@@ -4,7 +4,8 @@ The hot path of the reference's `WholeBodyController` (updateState -> solveQP ->
 computeJointTorques, src/whole_body_controller.cpp:650-652) as hand-written HIP for gfx950,
 behind the C-ABI in include/wbc.h.  This package is the Python view of that C-ABI:
 
-  Engine          batched handle (wbc_create ... wbc_get_output), see _capi.py
+  Engine          batched handle (wbc_create ... wbc_get_output), see _capi.py; per-robot controller
+                  parameters: Engine.set_robot_params / bind_device_robot_params / robot_params
   Planner         batched motion planner (WbcReferenceMsg producer), see _capi.py
   workloads       synthetic inputs of the BASELINE.json configurations
   sharding        robot shards and the per-step all-gather of the multi-GPU path
@@ -17,7 +18,8 @@ The product path has no CPU fallback: without libwbc_hip.so or a GPU it raises.
 """
 from ._capi import (COLD, DEBUG, FUSED, GROUP, NO_X, RESIDENT, SPLIT, STATELESS, TIMED, QP_INFEASIBLE, QP_MAX_ITER, QP_NUMERIC, QP_OK, Engine, WbcError,  # noqa: F401
                     WbcModel, WbcParams, anymal_model, default_params, load_library, model_from_urdf, split_debug, Planner,
-                    WbcPlannerParams)
+                    WbcPlannerParams, ROBOT_PARAM_NAMES, robot_param_table)
 
 __all__ = ["Engine", "Planner", "WbcPlannerParams", "model_from_urdf", "WbcError", "WbcModel", "WbcParams", "anymal_model", "default_params", "load_library",
-           "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC"]
+           "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC",
+           "ROBOT_PARAM_NAMES", "robot_param_table"]

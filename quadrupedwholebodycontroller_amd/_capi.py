@@ -17,6 +17,9 @@ NUM_JOINTS, NV, NC = 12, 42, 70
 POSE_LEN, NU_LEN, REF_LEN = 7, 18, 54
 STATELESS, DEBUG, NO_X, SPLIT, TIMED, COLD, FUSED, GROUP, RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128, 256
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
+# columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
+ROBOT_PARAM_NAMES = ("friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing", "slack_weight")
+RP_LEN = 10
 
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
@@ -27,7 +30,7 @@ C_API_SYMBOLS = [
     "wbc_default_params", "wbc_anymal_model", "wbc_create", "wbc_destroy", "wbc_batch", "wbc_set_stream",
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
-    "wbc_last_error", "wbc_model_from_urdf",
+    "wbc_last_error", "wbc_model_from_urdf", "wbc_set_robot_params", "wbc_bind_device_robot_params", "wbc_get_robot_params",
 ]
 
 
@@ -96,10 +99,14 @@ def load_library(path: str = LIB_PATH):
         "wbc_last_kernel_ms": ([P, dp], I32),
         "wbc_last_error": ([], C.c_char_p),
         "wbc_model_from_urdf": ([C.c_char_p, P, P, C.c_char_p, C.POINTER(WbcModel)], I32),
+        "wbc_set_robot_params": ([P, P], I32),
+        "wbc_bind_device_robot_params": ([P, P], I32),
+        "wbc_get_robot_params": ([P, P], I32),
     }
     for name, (argt, rest) in sig.items():
-        if name == "wbc_modes_per_wave" and not hasattr(lib, name):
-            continue  # a diagnostic entry point: earlier builds (A/B variants, tools/build_rev.sh) lack it
+        if name in ("wbc_modes_per_wave", "wbc_set_robot_params", "wbc_bind_device_robot_params",
+                    "wbc_get_robot_params") and not hasattr(lib, name):
+            continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
         fn.restype = rest
@@ -146,6 +153,29 @@ class WbcError(RuntimeError):
     pass
 
 
+def robot_param_table(batch: int, params: WbcParams, table) -> np.ndarray:
+    """The [B, RP_LEN] table of wbc_set_robot_params from an [B, 10] or [B, 9] array, or from a dict of
+    column name (ROBOT_PARAM_NAMES) -> scalar or length-B array, whose missing columns take the
+    engine-wide value of `params`.  The reserved column is 0."""
+    B = int(batch)
+    out = np.zeros((B, RP_LEN))
+    if isinstance(table, dict):
+        unknown = sorted(set(table) - set(ROBOT_PARAM_NAMES))
+        if unknown:
+            raise ValueError(f"unknown robot parameter columns {unknown}; columns are {ROBOT_PARAM_NAMES}")
+        for c, name in enumerate(ROBOT_PARAM_NAMES):
+            v = np.asarray(table[name], np.float64) if name in table else np.float64(getattr(params, name))
+            if v.ndim not in (0, 1) or (v.ndim == 1 and v.shape[0] != B):
+                raise ValueError(f"robot parameter {name}: need a scalar or {B} values, got shape {v.shape}")
+            out[:, c] = v
+        return out
+    t = np.asarray(table, np.float64)
+    if t.ndim != 2 or t.shape[0] != B or t.shape[1] not in (RP_LEN - 1, RP_LEN):
+        raise ValueError(f"robot parameter table: need shape ({B}, {RP_LEN}) or ({B}, {RP_LEN - 1}), got {t.shape}")
+    out[:, :RP_LEN - 1] = t[:, :RP_LEN - 1]
+    return out
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -154,6 +184,8 @@ class Engine:
         self.batch = int(batch)
         self.n_modes = 0
         self._stream = None  # the bound caller stream object (kept alive while bound)
+        self._rp_table = None  # the bound device table's owner (kept alive while bound)
+        self.params = WbcParams.from_buffer_copy(params) if params else default_params()  # the engine-wide wbc_params
         self.h = C.c_void_p()
         rc = self.lib.wbc_create(C.byref(model) if model else None, C.byref(params) if params else None,
                                  self.batch, int(device), C.byref(self.h))
@@ -168,6 +200,7 @@ class Engine:
             self.lib.wbc_destroy(self.h)  # synchronizes the bound stream, which is still alive here
             self.h = C.c_void_p()
         self._stream = None
+        self._rp_table = None
 
     def __del__(self):
         try:
@@ -203,6 +236,28 @@ class Engine:
         """Integer device pointers of caller-owned output buffers; 0 = engine-owned buffer."""
         v = [C.c_void_p(int(p)) if p else None for p in (tau, grf, x, status, iters)]
         self._check(self.lib.wbc_bind_device_outputs(self.h, *v), "wbc_bind_device_outputs")
+
+    def set_robot_params(self, table):
+        """wbc_set_robot_params: per-robot friction, max_torque, gains and slack_weight for the default
+        step.  `table`: an [B, 10] or [B, 9] array (columns ROBOT_PARAM_NAMES), or a dict of column name
+        to scalar or length-B array (missing columns: the engine's wbc_params); None clears the table."""
+        t = None if table is None else np.ascontiguousarray(robot_param_table(self.batch, self.params, table))
+        self._check(self.lib.wbc_set_robot_params(self.h, _ptr(t)), "wbc_set_robot_params")
+
+    def bind_device_robot_params(self, table=0):
+        """wbc_bind_device_robot_params: a caller-owned device table [B, 10] of doubles (no copy, no host
+        validation): an integer device pointer, or an object with data_ptr() (a torch tensor), which the
+        engine keeps referenced while it is bound.  0 / None: the engine-owned table, or none."""
+        ptr = int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table or 0)
+        self._check(self.lib.wbc_bind_device_robot_params(self.h, C.c_void_p(ptr) if ptr else None),
+                    "wbc_bind_device_robot_params")
+        self._rp_table = table if ptr else None
+
+    def robot_params(self) -> np.ndarray:
+        """wbc_get_robot_params: the [B, 10] table in force (without one: the engine-wide values in B rows)."""
+        out = np.zeros((self.batch, RP_LEN))
+        self._check(self.lib.wbc_get_robot_params(self.h, _ptr(out)), "wbc_get_robot_params")
+        return out
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

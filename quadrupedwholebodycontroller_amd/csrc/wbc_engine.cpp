@@ -24,6 +24,9 @@ extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStre
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update_solve(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_stance_step(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_rp0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
@@ -55,6 +58,13 @@ struct wbc_engine {
     wbc_params* d_params = nullptr;
     double* d_limg = nullptr;  // the step kernel's LDS image of the model + friction table (wbc_layout.h)
     wbc_params params{};  // host copy, passed by value in the kernel arguments (KernelArgs::pv)
+    // per-robot parameters (KernelArgs::rp, [B][WBC_RP_LEN]): the engine's own table (allocated at the
+    // first wbc_set_robot_params; rp_own: it holds a table), a caller's device table, and the one in
+    // force (the caller's, else the engine's own when set, else none: the engine-wide params)
+    double* d_rp = nullptr;
+    bool rp_own = false;
+    const double* rp_bound = nullptr;
+    const double* in_rp = nullptr;
     // owned inputs: one device block [pose | nu | qj | ref | contacts | switching] (so a host cycle
     // is one H2D copy), and the outputs one block [tau | grf | status | iters | x]
     void* d_inblk = nullptr;
@@ -164,6 +174,7 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) {
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
+    a.rp = h->in_rp;
     a.base_pose = h->in_pose;
     a.nu = h->in_nu;
     a.qj = h->in_qj;
@@ -528,7 +539,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_box) (void)hipHostFree(h->res_box);
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
-                    h->d_fb, h->d_dbg, h->d_qmap};
+                    h->d_fb, h->d_dbg, h->d_qmap, h->d_rp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -609,6 +620,62 @@ int32_t wbc_bind_device_outputs(wbc_engine* h, double* d_tau, double* d_grf, dou
     return WBC_OK;
 }
 
+int32_t wbc_set_robot_params(wbc_engine* h, const double* table) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (!table) {  // back to the engine-wide params (or to a caller's bound table)
+        h->rp_own = false;
+        h->in_rp = h->rp_bound;
+        return WBC_OK;
+    }
+    static const char* const names[WBC_RP_LEN - 1] = {"friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing",
+                                                      "slack_weight"};
+    const size_t B = (size_t)h->batch;
+    for (size_t b = 0; b < B; ++b) {
+        const int c = wbc::rp_bad_column(table + b * WBC_RP_LEN);
+        if (c >= 0) {
+            char val[32];
+            std::snprintf(val, sizeof(val), "%g", table[b * WBC_RP_LEN + c]);
+            return fail(WBC_ERR_ARG, "wbc_set_robot_params: row " + std::to_string(b) + ", column " + std::to_string(c) + " (" +
+                                         names[c] + ") = " + val +
+                                         ": need finite entries, friction >= 0, max_torque >= 0, slack_weight > 0");
+        }
+    }
+    WBC_HIP(sync_own(h));
+    WBC_HIP(hipSetDevice(h->device));
+    if (!h->d_rp && dalloc(&h->d_rp, B * WBC_RP_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_rp");
+    WBC_HIP(hipMemcpyAsync(h->d_rp, table, B * WBC_RP_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));  // the host table may be reused by the caller
+    h->rp_own = true;
+    if (!h->rp_bound) h->in_rp = h->d_rp;
+    return WBC_OK;
+}
+
+int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
+        return fail(WBC_ERR_ARG, "wbc_bind_device_robot_params: the table must be 16-byte aligned");
+    h->rp_bound = d_table;
+    h->in_rp = d_table ? d_table : (h->rp_own ? h->d_rp : nullptr);
+    return WBC_OK;
+}
+
+int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    const size_t B = (size_t)h->batch;
+    if (h->in_rp) {
+        WBC_HIP(sync_own(h));
+        WBC_HIP(hipSetDevice(h->device));
+        WBC_HIP(hipMemcpyAsync(table, h->in_rp, B * WBC_RP_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        WBC_HIP(hipStreamSynchronize(h->stream));
+    } else {
+        const wbc_params& p = h->params;
+        const double row[WBC_RP_LEN - 1] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight};
+        for (size_t b = 0; b < B; ++b) std::memcpy(table + b * WBC_RP_LEN, row, sizeof(row));
+    }
+    for (size_t b = 0; b < B; ++b) table[b * WBC_RP_LEN + WBC_RP_LEN - 1] = 0.0;
+    return WBC_OK;
+}
+
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
@@ -628,6 +695,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
+    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_update: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -640,6 +708,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_solve: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
+    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_solve: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
@@ -651,6 +720,10 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
+    if (h->in_rp && (flags & (WBC_SPLIT | WBC_FUSED)))
+        return fail(WBC_ERR_STATE, std::string("wbc_step: ") + ((flags & WBC_SPLIT) ? "WBC_SPLIT" : "WBC_FUSED") +
+                                       " with a per-robot parameter table in force (default form only; clear it with "
+                                       "wbc_set_robot_params(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
@@ -666,8 +739,12 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
         // default: one kernel, every QP reduced to 12 variables and solved in the update wave; a
         // stateless step whose masks the host knows to be all 15 (no map then) runs the stance-only
         // instance, scheduled for it alone (wbc_kernel_stance.hip)
+        // a per-robot parameter table in force: the same three choices among its own instances
+        // (wbc_kernel_rps.hip stance-only, wbc_kernel_rp0.hip stateless, wbc_kernel_rp1.hip stateful)
         WBC_HIP(begin_step16(h, a, flags));
-        if (step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step(&a, h->stream));
+        if (a.rp && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_rp(&a, h->stream));
+        else if (a.rp) WBC_HIP(a.stateful ? wbc_launch_update_solve_rp1(&a, h->stream) : wbc_launch_update_solve_rp0(&a, h->stream));
+        else if (step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step(&a, h->stream));
         else WBC_HIP(wbc_launch_update_solve(&a, h->stream));
     }
     if (timed) {
@@ -705,6 +782,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (!h->n_modes) return fail(WBC_ERR_STATE, "wbc_step_modes: no mode hypotheses set (wbc_set_modes)");
+    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_step_modes: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
     WBC_HIP(hipSetDevice(h->device));
@@ -880,6 +958,11 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_cycle: mode hypotheses are set");
     if (!base_pose || !nu || !qj || !ref || !contacts || !switching) return fail(WBC_ERR_ARG, "wbc_cycle: null input");
+    if (h->in_rp && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
+        return fail(WBC_ERR_STATE, std::string("wbc_cycle: ") +
+                                       ((flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT") +
+                                       " with a per-robot parameter table in force (plain cycle only; clear it with "
+                                       "wbc_set_robot_params(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     const size_t inb = in_block_bytes(B), outb = out_block_bytes(B);

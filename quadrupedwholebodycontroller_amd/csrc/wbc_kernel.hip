@@ -1697,7 +1697,19 @@ __device__ __forceinline__ int seg_shfl_i(int v, int j) {
 // rows; otherwise the four-contact stance form (stateless).  qp = output row, hr = history row.
 // STF: -1 stateful or not by KernelArgs::stateful at run time; 0 / 1 known at compile time (the
 // default step's two instances, wbc_update_solve_kernel<STF>)
-template <bool ROWS, bool GEN, int STF = -1>
+// RP (the per-robot-parameter instances, KernelArgs::rp): a.pv holds the segment's own robot's
+// values, and the workgroup's shared friction table, built for the engine-wide mu, gives way to the
+// robot's mu at the one position of a face's row that holds it (element 3 l + 2 of leg l's faces):
+// a select on the value read, so the table stays one per workgroup (four copies would not fit the
+// LDS budget of four workgroups per CU)
+template <bool RP>
+__device__ __forceinline__ double fric_elem(double tv, bool frc, int leg, int k, double mu) {
+    if constexpr (RP) {
+        if (k % 3 == 2) return (frc && k == 3 * leg + 2) ? mu : tv;
+    }
+    return tv;
+}
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
                         double hws_tag = 0.0) {
@@ -1890,7 +1902,10 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     nn = 0.0;
 #pragma unroll
-                    for (int k = 0; k < N; ++k) { np[k] = sgn * nrow[k]; nn = fma(np[k], np[k], nn); }
+                    for (int k = 0; k < N; ++k) {
+                        np[k] = sgn * fric_elem<RP>(nrow[k], frc, (p & 15) >> 2, k, pr.friction);
+                        nn = fma(np[k], np[k], nn);
+                    }
                 };
                 double na[N], nb[N], nna, nnb;
                 warm_row(pa, na, nna);
@@ -1976,7 +1991,10 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     double np[N], nn = 0.0;
 #pragma unroll
-                    for (int k = 0; k < N; ++k) { np[k] = sgn * nrow[k]; nn = fma(np[k], np[k], nn); }
+                    for (int k = 0; k < N; ++k) {
+                        np[k] = sgn * fric_elem<RP>(nrow[k], frc, (p & 15) >> 2, k, pr.friction);
+                        nn = fma(np[k], np[k], nn);
+                    }
                     double d2[N], rk, zn, zk, dq, jq;
                     direction(dot_col(jc, np), pos, d2, rk, zn, zk, dq, jq);
                     if (!(zn > 1e-26 * fmax(1.0, nn))) { fail = true; break; }  // dependent: reject
@@ -2088,7 +2106,8 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                 // dot then ends in one add instead of three)
                 double a2[2] = {0.0, 0.0};
 #pragma unroll
-                for (int k = 0; k < N; ++k) a2[k & 1] = fma(jc[k], nrow[k], a2[k & 1]);
+                for (int k = 0; k < N; ++k)
+                    a2[k & 1] = fma(jc[k], fric_elem<RP>(nrow[k], frc, (pstar & 15) >> 2, k, pr.friction), a2[k & 1]);
                 const double dn = a2[0] + a2[1];
                 dj = ((l < N) ? ((frc || (tq & 1)) ? 1.0 : -1.0) : 0.0) * dn;
             }
@@ -2333,7 +2352,8 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
     rsw = cmd - js_dot;
 }
 
-template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false>
+template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
+          bool RP = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr) {
@@ -3165,7 +3185,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             double hrow[12], gsv = 0.0;
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
-                solve16<true, false, STF>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK);
+                solve16<true, false, STF, RP>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK);
                 return true;
             }
             return false;
@@ -3175,8 +3195,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         bool vac = false;
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
-            solve16<true, true, STF>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi,
-                                     hWtag);
+            solve16<true, true, STF, RP>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi,
+                                         hWtag);
             return true;
         }
         return false;
@@ -4440,7 +4460,7 @@ struct SolveLds {
 // wbc_kernel_modes.hip) include this file under their own macro, which keeps only their kernel and
 // its launcher; this file's own unit builds everything else
 #if defined(WBC_STANCE_TU) || defined(WBC_STEP0_TU) || defined(WBC_STEP1_TU) || defined(WBC_MODES_TU) || \
-    defined(WBC_RESIDENT_TU)
+    defined(WBC_RESIDENT_TU) || defined(WBC_RP0_TU) || defined(WBC_RP1_TU) || defined(WBC_RPS_TU)
 #define WBC_SINGLE_TU 1
 #endif
 #ifndef WBC_SINGLE_TU
@@ -4550,6 +4570,21 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // kernel; a callee has no kernarg pointer of its own).
 // (One instance per calling kernel, TAG: a shared callee is allocated for the larger of its callers'
 // register budgets, which raised the default step's to 512 registers and its scratch to 2.2 KB.)
+// The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
+// does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
+__device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base, const double* r, bool bad) {
+    pv.friction = bad ? base.friction : r[WBC_RP_FRICTION];
+    pv.max_torque = bad ? base.max_torque : r[WBC_RP_MAX_TORQUE];
+    pv.kp = bad ? base.kp : r[WBC_RP_KP];
+    pv.kp_z = bad ? base.kp_z : r[WBC_RP_KP_Z];
+    pv.kd = bad ? base.kd : r[WBC_RP_KD];
+    pv.ki = bad ? base.ki : r[WBC_RP_KI];
+    pv.kp_swing = bad ? base.kp_swing : r[WBC_RP_KP_SWING];
+    pv.kd_swing = bad ? base.kd_swing : r[WBC_RP_KD_SWING];
+    pv.slack_weight = bad ? base.slack_weight : r[WBC_RP_SLACK_WEIGHT];
+}
+// (TAG >= 6: the per-robot-parameter instances, KernelArgs::rp: each fallback QP is solved under its
+// own robot's row, as its reduction was attempted)
 template <int TAG>
 __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, unsigned long long fm, int qp,
                                                           SolveLds* L) {
@@ -4561,6 +4596,13 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
         const int seg = __builtin_ctzll(fm) / UPD_SUB;
         fm &= fm - 1ull;
         wsync();
+        if constexpr (TAG >= 6) {
+            const double* r = f.rp + (size_t)__builtin_amdgcn_readlane(qp, seg * UPD_SUB) * WBC_RP_LEN;
+            double rv[WBC_RP_LEN - 1];
+#pragma unroll
+            for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
+            rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
+        }
         solve_general_qp(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
@@ -4573,7 +4615,12 @@ __device__ __forceinline__ int xcd_block(int b, int n) {
     return x * per + min(x, rem) + i;
 }
 // Two instances: STF = 0 for stateless steps (no history code at all), 1 for stateful ones
-template <int STF, bool SONLY = false>
+// RP: the per-robot-parameter instances (wbc_kernel_rp0.hip, wbc_kernel_rp1.hip, and the stance-only
+// wbc_kernel_rps.hip): each segment takes friction, max_torque, the gains and slack_weight from row
+// qp of KernelArgs::rp (indexed by the QP, never by the wave slot: a mapped, padding or
+// empty-workgroup segment reads the row of the QP it computes), the other parameters from
+// KernelArgs::pv.  No mode hypotheses (the launchers refuse).
+template <int STF, bool SONLY = false, bool RP = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
@@ -4627,12 +4674,38 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     // the robot's inputs (HBM) are requested before the model staging waits for its own loads
     double vin[(91 + UPD_SUB - 1) / UPD_SUB];
     load_inputs<UPD_SUB>(a, row, lane, vin);
+    // the QP's parameter row, requested with its inputs (one HBM round trip; every lane of the
+    // segment loads the same 80 bytes, as five 16-byte loads)
+    [[maybe_unused]] double rpv[WBC_RP_LEN];
+    if constexpr (RP) {
+        const double2* r2 = reinterpret_cast<const double2*>(a.rp + (size_t)qp * WBC_RP_LEN);
+#pragma unroll
+        for (int c = 0; c < WBC_RP_LEN / 2; ++c) {
+            const double2 w = r2[c];
+            rpv[2 * c] = w.x;
+            rpv[2 * c + 1] = w.y;
+        }
+    }
     // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy
     stage_to_lds<LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
     if (__all(empty)) return;  // the unused tail of a device-built map (uniform)
     lds_sync();
-    const bool solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY>(a, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr,
+    bool solved;
+    if constexpr (RP) {
+        // the segment's own arguments: pv with the row's nine values (per-lane registers from here
+        // on; every device function reads its parameters through KernelArgs::pv).  A row the step does
+        // not accept keeps the engine-wide values and marks the robot's inputs non-finite: the
+        // existing flagged-input path (Prob::flags bit 1: WBC_QP_NUMERIC, zero outputs)
+        KernelArgs ar = a;
+        const bool bad = rp_bad_column(rpv) >= 0;
+        rp_apply(ar.pv, a.pv, rpv, bad);
+        if (bad) vin[0] = __builtin_nan("");
+        solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true>(ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg],
+                                                                                nullptr, L.model, &L.fric[0], vin);
+    } else {
+        solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY>(a, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr,
                                                                          L.model, &L.fric[0], vin);
+    }
     // a QP whose reduction was not usable: its problem goes to work row qp, and the wave solves it
     // with the general 24-variable method right here (drain_fallbacks, the rare path; the wave's
     // LDS is reused once the four segments are done)
@@ -4650,7 +4723,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<2 + STF>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<(RP ? 6 : 2) + STF>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -5129,6 +5202,29 @@ extern "C" hipError_t wbc_preload_resident() {
     hipError_t e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&wbc::wbc_resident_kernel<1>));
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&wbc::wbc_resident_kernel<0>));
     return e;
+}
+#elif defined(WBC_RP0_TU)
+// The default step under a per-robot parameter table (KernelArgs::rp), stateless, any mask mix
+// (wbc_kernel_rp0.hip, Makefile RP0_KFLAGS)
+extern "C" hipError_t wbc_launch_update_solve_rp0(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || a->stateful || a->modes || !a->rp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, false, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+#elif defined(WBC_RPS_TU)
+// The stance-only default step under a per-robot parameter table (wbc_kernel_rps.hip, Makefile
+// RPS_KFLAGS): stateless, every mask 15, as wbc_launch_stance_step
+extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || a->stateful || a->modes || a->qmap || !a->rp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+#elif defined(WBC_RP1_TU)
+// The stateful default step under a per-robot parameter table (wbc_kernel_rp1.hip, Makefile RP1_KFLAGS)
+extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || !a->stateful || a->modes || !a->rp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<1, false, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
 }
 #else
 extern "C" hipError_t wbc_launch_update_solve0(const wbc::KernelArgs* a, hipStream_t st);

@@ -1,0 +1,7 @@
+// wbc_kernel_rps.hip — the stance-only default step under a per-robot parameter table
+// (wbc_update_solve_kernel<0, true, true>, KernelArgs::rp): a stateless step whose
+// QPs all have contact mask 15, the general 12-variable form compiled out, as wbc_kernel_stance.hip.
+// A translation unit of its own (Makefile RPS_KFLAGS); the code is wbc_kernel.hip's, which
+// WBC_RPS_TU limits to this one kernel and its launcher.
+#define WBC_RPS_TU 1
+#include "wbc_kernel.hip"

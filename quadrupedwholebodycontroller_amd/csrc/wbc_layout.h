@@ -187,6 +187,11 @@ struct KernelArgs {
     // compiler knows is constant), not through `params`, whose global loads it must repeat after
     // every global store and wait for in turn
     wbc_params pv;
+    // Per-robot parameters (wbc_set_robot_params / wbc_bind_device_robot_params): [batch][WBC_RP_LEN],
+    // row qp for QP qp; read only by the per-robot instances of the default step (wbc_kernel_rps.hip,
+    // wbc_kernel_rp0.hip, wbc_kernel_rp1.hip), which take the nine values of their QP's row in place
+    // of pv's.  Last, so that no other argument's offset moves.
+    const double* rp;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -199,6 +204,17 @@ constexpr int QMAP_MAX_BATCH = (1 << 27) - 1;  // qp << 4 fits 31 bits
 #else
 #define WBC_HD
 #endif
+// A per-robot parameter row (wbc.h WBC_RP_*) the step accepts: -1, or the first column that fails
+// (a non-finite entry in columns 0-8, friction < 0, max_torque < 0, slack_weight <= 0).  One
+// definition for the host's validation (wbc_set_robot_params) and the kernels' (a device-bound row).
+WBC_HD inline int rp_bad_column(const double* r) {
+    for (int c = 0; c < WBC_RP_LEN - 1; ++c) {
+        const bool neg = (c == WBC_RP_FRICTION || c == WBC_RP_MAX_TORQUE) ? r[c] < 0.0
+                       : (c == WBC_RP_SLACK_WEIGHT)                       ? r[c] <= 0.0 : false;
+        if (!__builtin_isfinite(r[c]) || neg) return c;
+    }
+    return -1;
+}
 WBC_HD inline int32_t qmap_entry(int qp, int mask) { return (int32_t)((qp << 4) | (mask & 15)); }
 constexpr int QMAP_SEG = 4;  // QPs per wave (UPD_RPW of the kernel)
 // Layout.  The general 12-variable form runs one instruction stream for every contact mask, so

@@ -1,0 +1,109 @@
+"""CPU: the per-robot parameter table's Python forms (quadrupedwholebodycontroller_amd.robot_param_table,
+what Engine.set_robot_params passes to wbc_set_robot_params) and the compiler's resource report of the
+kernel units that read the table (wbc_kernel_rp0.hip, wbc_kernel_rp1.hip, wbc_kernel_rps.hip).
+
+wbc_set_robot_params validates on the host, but it needs an engine and an engine needs a device, so
+the validation's test is tests/test_gpu_robot_params.py's."""
+import os
+import re
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import wbc_ref as R
+from quadrupedwholebodycontroller_amd import ROBOT_PARAM_NAMES, _capi, robot_param_table
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
+
+
+def test_names_follow_the_header():
+    hdr = open(os.path.join(ROOT, "include", "wbc.h")).read()
+    cols = {n: int(v) for n, v in re.findall(r"WBC_RP_(\w+) = (\d+)", hdr)}
+    assert cols.pop("LEN") == _capi.RP_LEN == 10
+    assert [n.lower() for n, _ in sorted(cols.items(), key=lambda kv: kv[1])] == list(ROBOT_PARAM_NAMES)
+    assert sorted(cols.values()) == list(range(9))
+    for s in ("wbc_set_robot_params", "wbc_bind_device_robot_params", "wbc_get_robot_params"):
+        assert s in _capi.C_API_SYMBOLS and re.search(rf"int32_t {s}\(", hdr)
+
+
+def test_table_forms():
+    _, p = R.model_params()
+    B = 6
+    g = np.random.default_rng(3)
+    full = g.uniform(1.0, 2.0, (B, 10))
+    t = robot_param_table(B, p, full)
+    assert t.shape == (B, 10) and np.array_equal(t[:, :9], full[:, :9]) and not t[:, 9].any()
+    assert np.array_equal(robot_param_table(B, p, full[:, :9]), t)
+    # the dict form: scalars and length-B arrays, missing columns from the engine's wbc_params
+    mu = g.uniform(0.4, 1.2, B)
+    d = robot_param_table(B, p, {"friction": mu, "kp_swing": 300})
+    assert np.array_equal(d[:, 0], mu) and np.all(d[:, 6] == 300.0) and not d[:, 9].any()
+    for c, n in enumerate(ROBOT_PARAM_NAMES):
+        if n not in ("friction", "kp_swing"):
+            assert np.all(d[:, c] == getattr(p, n)), n
+    assert np.array_equal(robot_param_table(B, p, {})[:, :9], np.tile([getattr(p, n) for n in ROBOT_PARAM_NAMES], (B, 1)))
+    for bad in (full[:5], full[:, :8], full.ravel(), {"mu": 1.0}, {"kp": np.ones(B + 1)}, {"kp": np.ones((B, 1))}):
+        with pytest.raises(ValueError):
+            robot_param_table(B, p, bad)
+
+
+def _report(unit, var):
+    """The compiler's resource report (-Rpass-analysis=kernel-resource-usage) of a one-kernel unit
+    under its Makefile flags, {kernel: {field: value}}, and its device assembly."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    waves = re.search(r"^WAVES \?= (\d+)", mk, re.M).group(1)
+    kflags = re.search(r"^KFLAGS := (.*)$", mk, re.M).group(1).split()
+    sflags = re.search(rf"^{var} := (.*)$", mk, re.M).group(1).split()
+    assert unit in re.search(r"^KTU := (.*)$", mk, re.M).group(1).split()
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"),
+                        "-I", CSRC, f"-DWBC_WAVES_PER_SIMD={waves}", *kflags, *sflags, "-S", "--offload-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, f"wbc_kernel_{unit}.hip"), "-o", "-"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out, cur = {}, None
+    for line in r.stderr.split("\n"):
+        m = re.search(r"remark:\s+(.*?):\s+(\S+) \[-Rpass-analysis", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            cur = out.setdefault(m.group(2), {})
+        elif cur is not None and m.group(2).isdigit():
+            cur[m.group(1)] = int(m.group(2))
+    return out, r.stdout
+
+
+@pytest.mark.parametrize("unit,var,kernel,base,base_var", [
+    ("rp0", "RP0_KFLAGS", "wbc_update_solve_kernelILi0ELb0ELb1E", "step0", "STEP0_KFLAGS"),
+    ("rp1", "RP1_KFLAGS", "wbc_update_solve_kernelILi1ELb0ELb1E", "step1", "STEP1_KFLAGS"),
+    ("rps", "RPS_KFLAGS", "wbc_update_solve_kernelILi0ELb1ELb1E", "stance", "STANCE_KFLAGS"),
+])
+def test_new_units_resources(unit, var, kernel, base, base_var):
+    """The per-robot instances keep the default step's footprint: at most 40 960 B of LDS (four
+    workgroups per CU), one wave per SIMD as the instance they stand in for, and no scratch of their
+    own.  The report's scratch size of a kernel includes its callees' frames, and the default step's
+    kernels all call drain_fallbacks (the rare general solve, whose frame is the 900-odd bytes the
+    report shows for the existing instances too, tests/test_kernel_resources.py): so the kernel's own
+    scratch is 0 when the report shows no more than the callee alone needs, which is what the existing
+    instance reports; and, as tests/test_kernel_resources.py checks the existing units, the kernel's
+    own body holds no scratch instruction and the unit holds the kernel and its fallback callee only."""
+    with ThreadPoolExecutor(2) as ex:
+        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+    assert len(new) == 1 and len(old) == 1, (list(new), list(old))
+    (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
+    assert kernel in name, name
+    print(unit, rep, "against", base, ref)
+    assert rep["LDS Size [bytes/block]"] <= 40960, rep
+    assert rep["Occupancy [waves/SIMD]"] == ref["Occupancy [waves/SIMD]"] == 1, (rep, ref)
+    assert rep["ScratchSize [bytes/lane]"] <= ref["ScratchSize [bytes/lane]"], (rep, ref)
+    assert rep["VGPRs"] + rep["AGPRs"] <= 512, rep
+    lines = asm.split("\n")
+    starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]
+    ends = [i for i, l in enumerate(lines) if l.startswith(".Lfunc_end")]
+    assert len(starts) == 2 and sum("drain_fallbacks" in n for _, n in starts) == 1, [n for _, n in starts]
+    for i, n in starts:
+        if "drain_fallbacks" not in n:
+            body = lines[i:min(x for x in ends if x > i)]
+            assert not [l for l in body if "scratch_" in l], n
