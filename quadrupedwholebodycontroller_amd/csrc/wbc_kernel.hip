@@ -378,6 +378,38 @@ __device__ __forceinline__ double seg_sum(double v) {
         else return swz_head<0x00>(v);
     }
 }
+// Six segment sums at once.  16 lanes: a halving butterfly.  After the first step (partner lane
+// i ^ 8) a partial sum is needed in eight lanes only, so each register carries two quantities, one
+// per lane group, then four (row_ror:4), then all six (row_ror:2), and the last step (row_ror:1)
+// runs once for the six; row_newbcast hands each result to the segment.  row_ror:n gives lane i the
+// value of lane i - n, so the groups are chosen for every kept lane to find its own quantity
+// there: A in lanes 9..15 and 0, B in 1..8; C in 5..12, D in 13..4; E in 7..14, F in 15..6.  The
+// additions of each quantity pair as in seg_sum (i with i + 8, then + 4, + 2, + 1 as seen from lane
+// 0) and addition commutes, so every result has seg_sum's bits: 47 instructions instead of 78.
+template <int SUB>
+__device__ __forceinline__ void seg_sum6(double (&t)[6]) {
+    if constexpr (SUB != 16) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t[k] = seg_sum<SUB>(t[k]);
+    } else {
+        const int ln = (int)threadIdx.x & 15;
+        const bool kA = ((ln - 1) & 15) >= 8, kC = ((ln - 5) & 15) < 8, kE = ((ln - 7) & 15) < 8;
+        const bool k2 = ((ln - 5) & 7) < 4, k3 = ((ln + 1) & 3) < 2;
+        const double ab = (kA ? t[0] : t[1]) + dpp_d<0x128>(kA ? t[1] : t[0]);
+        const double cd = (kC ? t[2] : t[3]) + dpp_d<0x128>(kC ? t[3] : t[2]);
+        double ef = (kE ? t[4] : t[5]) + dpp_d<0x128>(kE ? t[5] : t[4]);
+        const double p = (k2 ? ab : cd) + dpp_d<0x124>(k2 ? cd : ab);
+        ef += dpp_d<0x124>(ef);
+        double x = (k3 ? p : ef) + dpp_d<0x122>(k3 ? ef : p);
+        x += dpp_d<0x121>(x);
+        t[0] = dpp_d<0x150>(x);
+        t[1] = dpp_d<0x158>(x);
+        t[2] = dpp_d<0x15C>(x);
+        t[3] = dpp_d<0x154>(x);
+        t[4] = dpp_d<0x15E>(x);
+        t[5] = dpp_d<0x156>(x);
+    }
+}
 template <int SUB>
 __device__ __forceinline__ bool seg_any(bool p) {
     if constexpr (SUB == 64) {
@@ -966,31 +998,36 @@ __device__ bool stance_reduce([[maybe_unused]] const KernelArgs& ka, [[maybe_unu
     // H^ rows (lane a < 6) over S: H^ = I + Mb^-2 + Mb^-1 Q Mb^-1, Mb^-1 = diag(I / m, I_c^-1)
     {
         const int ra = lane < 6 ? lane : 5;
-        // T = Q Mb^-1, rows ra (lin) or 3..5 (ang, then I_c^-1 from the left)
+        const bool lin = ra < 3;
+        // T = Q Mb^-1, rows ra (lin) or 3..5 (ang, then I_c^-1 from the left).  One form for both
+        // kinds of lane, the left factor selected by value: a lin lane's row is (1 / m) T_ra, an ang
+        // lane's I_c^-1[a3] . (T_3, T_4, T_5), so with weights (1 / m, 0, 0) a lin lane runs the ang
+        // lane's instructions to the same bits (fma(0, finite, t) = t); as two branches the wave
+        // issued both sides, each with its own LDS loads and waits, and hr[ra] += ... was a select
+        // chain over the six entries.  The sums are spelled as the compiler contracted the branches'
+        // x a + y b + z c: fma(z, c, fma(x, a, y b)).
         auto qm = [&](int row, double* o) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) o[c] = R.Q[row][c] * inv_m;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                o[3 + c] = R.Q[row][3] * P.Icinv[c] + R.Q[row][4] * P.Icinv[3 + c] + R.Q[row][5] * P.Icinv[6 + c];
+                o[3 + c] = fma(R.Q[row][5], P.Icinv[6 + c], fma(R.Q[row][3], P.Icinv[c], R.Q[row][4] * P.Icinv[3 + c]));
         };
-        double hr[6];
-        if (ra < 3) {
-            qm(ra, hr);
+        double hr[6], t3[3][6];
+        qm(lin ? ra : 3, t3[0]); qm(4, t3[1]); qm(5, t3[2]);
+        const double* ic = &P.Icinv[lin ? 0 : 3 * (ra - 3)];
+        const double w0 = lin ? inv_m : ic[0], w1 = lin ? 0.0 : ic[1], w2 = lin ? 0.0 : ic[2];
+        const double dg = lin ? fma(inv_m, inv_m, 1.0) : 1.0;  // the diagonal of I + Mb^-2's lin block
 #pragma unroll
-            for (int c = 0; c < 6; ++c) hr[c] *= inv_m;
-            hr[ra] += 1.0 + inv_m * inv_m;
-        } else {
-            double t3[3][6];
-            qm(3, t3[0]); qm(4, t3[1]); qm(5, t3[2]);
-            const int a3 = ra - 3;
-            const double* ic = &P.Icinv[3 * a3];
+        for (int c = 0; c < 6; ++c) {
+            hr[c] = fma(w2, t3[2][c], fma(w0, t3[0][c], w1 * t3[1][c]));
+            hr[c] += (c == ra) ? dg : 0.0;
+        }
+        {   // (I_c^-2)[a3][c] on the ang lanes
+            const double v0 = lin ? 0.0 : ic[0];
 #pragma unroll
-            for (int c = 0; c < 6; ++c) hr[c] = ic[0] * t3[0][c] + ic[1] * t3[1][c] + ic[2] * t3[2][c];
-            hr[ra] += 1.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c)  // (I_c^-2)[a3][c]
-                hr[3 + c] += ic[0] * P.Icinv[c] + ic[1] * P.Icinv[3 + c] + ic[2] * P.Icinv[6 + c];
+            for (int c = 0; c < 3; ++c)
+                hr[3 + c] += fma(w2, P.Icinv[6 + c], fma(v0, P.Icinv[c], w1 * P.Icinv[3 + c]));
         }
         // v -> Mb^-1 v (uniform, every lane) for g_f
         lds_sync();  // all reads of S's z column done
@@ -2622,6 +2659,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             for (int i = 0; i < 9; ++i) bd.I[i] = I[i];
         }
         // mass-weighted sums over the 13 bodies (lanes >= 13 hold mb = 0)
+        // (one at a time: the product is contracted into the first step's addition, an fma in the lane
+        // that keeps it, which the packed butterfly of seg_sum6 cannot reproduce for lane 8's half)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             cd[i] = seg_sum<SUB>(mb * vc[i]);
@@ -2664,8 +2703,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             t[4] = bd.I[2] - mb * d[0] * d[2];
             t[5] = bd.I[5] - mb * d[1] * d[2];
         }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) t[k] = seg_sum<SUB>(t[k]);
+        seg_sum6<SUB>(t);
         Ic[0] = t[0]; Ic[4] = t[1]; Ic[8] = t[2];
         Ic[1] = Ic[3] = t[3]; Ic[2] = Ic[6] = t[4]; Ic[5] = Ic[7] = t[5];
         inv3(Ic, Icinv);
@@ -2679,8 +2717,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
 #pragma unroll
             for (int i = 0; i < 3; ++i) { hb[i] = bd.F[i]; hb[3 + i] = t[i] + bd.N[i]; }
         }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) hb[k] = seg_sum<SUB>(hb[k]);
+        seg_sum6<SUB>(hb);
     }
     UST(a, rb, 5);
     // stage C: per joint: centroidal momentum column (about c), leg block of M, joint bias (C nu)_j
@@ -2767,15 +2804,23 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
     // h' = C nu + M[:, 0:6] y ; M_bb = [[m I, -m S(r)], [m S(r), I_c - m S(r)^2]] ; zeta = Mbar_b^-1 Ad^T h'_b
     double hp[6], zeta[6];
     {
-        double t[3], u[3], w[3], Icy[3];
-        cross3(r, &y[3], t);
-        cross3(r, t, u);
-        mv3(Ic, &y[3], Icy);
-        cross3(r, y, w);
+        double t[3];
+        if constexpr (STF == 0) {
+            // a stateless instance: y is zero by construction, so h' = C nu (x * 0.0 is not folded,
+            // x may be inf: written out, the y terms were ~30 issued instructions)
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            hp[i] = hb[i] + m * (y[i] - t[i]);
-            hp[3 + i] = hb[3 + i] + m * w[i] + Icy[i] - m * u[i];
+            for (int i = 0; i < 6; ++i) hp[i] = hb[i];
+        } else {
+            double u[3], w[3], Icy[3];
+            cross3(r, &y[3], t);
+            cross3(r, t, u);
+            mv3(Ic, &y[3], Icy);
+            cross3(r, y, w);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                hp[i] = hb[i] + m * (y[i] - t[i]);
+                hp[3 + i] = hb[3 + i] + m * w[i] + Icy[i] - m * u[i];
+            }
         }
         double hca[3];
         cross3(r, hp, t);
@@ -2871,9 +2916,12 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             Mij -= s.A[i][3] * KAj[0] + s.A[i][4] * KAj[1] + s.A[i][5] * KAj[2];
             mcol[i] = Mij;
         }
-        double t[3];
-        cross3(r, Alj, t);
-        const double hpj = s.hj[j] + dot3(Alj, y) + (t[0] + Aaj[0]) * y[3] + (t[1] + Aaj[1]) * y[4] + (t[2] + Aaj[2]) * y[5];
+        double hpj = s.hj[j];
+        if constexpr (STF != 0) {  // (y = 0 on a stateless instance, as for h' above)
+            double t[3];
+            cross3(r, Alj, t);
+            hpj = hpj + dot3(Alj, y) + (t[0] + Aaj[0]) * y[3] + (t[1] + Aaj[1]) * y[4] + (t[2] + Aaj[2]) * y[5];
+        }
         const double dj = s.pf[lj][kj] - sel3(c, kj);
 #pragma unroll
         for (int i = 0; i < 12; ++i) P.Mbj[i * 12 + j] = mcol[i];
@@ -4659,6 +4707,10 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
             kap = a.contacts[row] & 15;
         }
     }
+    // the stance-only instances run on the host's own masks, every one counted as 15 when they were
+    // copied (step_all_stance): a constant, so the mask byte is not loaded and the bounds' contact
+    // factors fold
+    if constexpr (SONLY) kap = 15;
     UST(a, qp, 30);  // kernel entry (diagnostic build)
 #ifdef WBC_ISTAMPS
     // placement and the constant clock, for the wave-schedule probe (tools/wave_sched.py): slots

@@ -2,9 +2,12 @@
 default step, wbc_kernel_step0.hip), per basic block, from the `make listing` output (hipcc -S
 -gline-tables-only; the stance-only step: build/wbc_kernel_stance.s with --sym of its instance).
 
-A loop is the set of blocks the listing marks "in Loop: Header=BB..": the stance form's and the
-general form's loops.  For each, prints every block (instructions, VALU / DPP / LDS / SALU / waits /
-nops / branches, the wbc_kernel.hip source lines it came from) and the totals of the blocks outside
+A loop is the set of blocks the listing marks "in Loop: Header=BB.." (the stance form's and the
+general form's loops) that lie on a cycle through the header: reachable from it and reaching it
+again by fall-through and branch edges inside that set.  A block that carries the loop's label but
+is on no such cycle (a side exit laid out between the loop's blocks, e.g. record stores after the last
+pass) is listed with [off-cycle] and charged to neither total.  For each loop, prints every block
+(instructions, VALU / DPP / LDS / SALU / waits / nops / branches, the wbc_kernel.hip source lines it came from) and the totals of the blocks outside
 the Givens drop path (source lines of the drop branch), i.e. the static length of an add pass.
 
 Usage: python tools/isa_loop.py [listing.s] [--sym NAME] [--quiet]"""
@@ -22,6 +25,34 @@ def drop_lines(src):
     a = next(i for i in range(sv, len(lines)) if "drop slot l1" in lines[i]) + 1
     b = next(i for i in range(a, len(lines)) if re.match(r"\s*mirror\(\);", lines[i])) + 1
     return a, b
+
+
+def on_cycle(header, bl, blocks, label):
+    """Indices of the loop's blocks on a cycle through its header (edges: fall-through to the next
+    block of the listing, branch targets; only edges between blocks of the loop)."""
+    inside = {b["idx"] for b in bl}
+    succ = {}
+    for b in bl:
+        out = [label[t]["idx"] for t in b["targets"] if t in label]
+        if b["falls"] and b["idx"] + 1 < len(blocks):
+            out.append(b["idx"] + 1)
+        succ[b["idx"]] = [x for x in out if x in inside]
+    head = label[header]["idx"] if header in label else bl[0]["idx"]
+
+    def closure(edges):
+        seen, todo = {head}, [head]
+        while todo:
+            for x in edges.get(todo.pop(), ()):
+                if x not in seen:
+                    seen.add(x)
+                    todo.append(x)
+        return seen
+
+    pred = {}
+    for a, outs in succ.items():
+        for x in outs:
+            pred.setdefault(x, []).append(a)
+    return closure(succ) & closure(pred)
 
 
 def main():
@@ -52,7 +83,7 @@ def main():
             hdr = re.search(r"Header=(BB\d+_\d+)", s)
             me = re.search(r"(BB\d+_\d+)", s.replace("%bb.", "BB_"))
             blk = dict(name=s.split()[0] if not s.startswith(";") else s[2:].split()[0], loop=hdr.group(1) if hdr else None,
-                       c=collections.Counter(), src=set(), n=0)
+                       c=collections.Counter(), src=set(), n=0, targets=[], falls=True, idx=len(blocks))
             if "=>This Inner Loop Header" in s:
                 blk["loop"] = "BB" + s.split(":")[0][4:]
             blocks.append(blk)
@@ -63,6 +94,9 @@ def main():
             continue
         op = s.split()[0]
         blk["n"] += 1
+        blk["falls"] = op not in ("s_branch", "s_endpgm", "s_setpc_b64")
+        if "branch" in op:
+            blk["targets"] += re.findall(r"\.L(BB\d+_\d+)", s)
         if curf.endswith("wbc_kernel.hip") and cur > 700:
             blk["src"].add(cur)
         c = blk["c"]
@@ -86,9 +120,15 @@ def main():
     for b in blocks:
         if b["loop"]:
             loops.setdefault(b["loop"], []).append(b)
+    label = {b["name"].rstrip(":").lstrip(".").replace("L", "", 1): b for b in blocks if b["name"].startswith(".LBB")}
     for name, bl in loops.items():
         tot, add = collections.Counter(), collections.Counter()
+        on = on_cycle(name, bl, blocks, label)
         for b in bl:
+            if b["idx"] not in on:
+                if not quiet:
+                    print(f"  {b['name']:14s} {b['n']:4d} {dict(b['c'])}  [off-cycle]")
+                continue
             tot.update(b["c"])
             tot["instr"] += b["n"]
             indrop = bool(b["src"]) and all(d0 <= x <= d1 for x in b["src"])
@@ -98,7 +138,7 @@ def main():
             if not quiet:
                 rng = (min(b["src"]), max(b["src"])) if b["src"] else None
                 print(f"  {b['name']:14s} {b['n']:4d} {dict(b['c'])} src {rng}{'  [drop]' if indrop else ''}")
-        print(f"loop {name}: {len(bl)} blocks, all {dict(tot)}")
+        print(f"loop {name}: {len(bl)} blocks ({len(bl) - len([b for b in bl if b['idx'] in on])} off-cycle, not counted), all {dict(tot)}")
         print(f"loop {name}: outside the drop path {dict(add)}")
 
 

@@ -5,12 +5,20 @@ instructions of inlined helpers (cross3, mv3, fast_rsq ...) go to the stage that
 Dividing a stage's measured ticks (ust16.py) by its VALU count separates issue-bound stages (~7 ticks
 per VALU instruction at one wave per SIMD) from latency-bound ones.
 
-Usage: python tools/isa_stages.py listing.s  (make -C quadrupedwholebodycontroller_amd/csrc listing)"""
+Usage: python tools/isa_stages.py [listing.s] [source.hip] [--sym NAME]
+(make -C quadrupedwholebodycontroller_amd/csrc build/wbc_kernel_stance.s; the default symbol is the
+stance-only stateless instance of that unit, wbc_update_solve_kernel<0, true, false>; the mixed-form
+instance of build/wbc_kernel_step0.s is --sym _ZN3wbc23wbc_update_solve_kernelILi0ELb0ELb0EEEvNS_10KernelArgsE)"""
 import collections
+import os
 import re
 import sys
 
-SYM = "_ZN3wbc23wbc_update_solve_kernelILi0EEEvNS_10KernelArgsE"  # the stateless instance
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
+SYM = "_ZN3wbc23wbc_update_solve_kernelILi0ELb1ELb0EEEvNS_10KernelArgsE"  # the stance-only stateless instance
+# a device function's first line, with or without __forceinline__
+FN = r"^__device__ (__forceinline__ )?%s %s\("
 
 
 def stage_ranges(src):
@@ -23,27 +31,29 @@ def stage_ranges(src):
                 return i + 1
         raise KeyError(pat)
 
-    up = find(r"^__device__ bool update_phase\(")
+    up = find(FN % ("bool", "update_phase"))
+    up_end = find(r"^}", up)
     u = [find(r"UST\(a, rb, %d\);" % k, up) for k in range(11)]
-    sr = find(r"^__device__ bool stance_reduce\(")
+    sr = find(FN % ("bool", "stance_reduce"))
     s19, s20, s12 = find(r"UST\(ka, rb, 19\)", sr), find(r"UST\(ka, rb, 20\)", sr), find(r"UST\(ka, rb, 12\)", sr)
     s21, s22, s13 = find(r"UST\(ka, rb, 21\)", sr), find(r"UST\(ka, rb, 22\)", sr), find(r"UST\(ka, rb, 13\)", sr)
     s14 = find(r"UST\(ka, rb, 14\)", sr)
-    r6 = find(r"^__device__ (__forceinline__ )?bool rank6_factor\(")
-    rg = find(r"^__device__ bool reduce_general\(")
+    r6 = find(FN % ("bool", "rank6_factor"))
+    rg = find(FN % ("bool", "reduce_general"))
     g20, g21, g22 = find(r"UST\(ka, rb, 20\)", rg), find(r"UST\(ka, rb, 21\)", rg), find(r"UST\(ka, rb, 22\)", rg)
     g14 = find(r"UST\(ka, rb, 14\)", rg)
-    sv = find(r"^__device__ void solve16\(")
+    sv = find(FN % ("void", "solve16"))
     s15, s16, s18 = find(r"UST\(a, rb, 15\)", sv), find(r"UST\(a, rb, 16\)", sv), find(r"UST\(a, rb, 18\)", sv)
     kern = find(r"void wbc_update_solve_kernel\(KernelArgs a\)")
+    kern_end = find(r"^}", kern)
     names = ["inputs+sincos", "stage A", "stage B", "Jf + CoM", "Ic", "stage C", "hb, y, zeta", "Jbar/Mbar/bbar",
              "Tdot_inv", "bounds, wrench, history"]
     r = collections.OrderedDict()
-    r["prologue (kernel)"] = (kern, kern + 60)
+    r["prologue (kernel)"] = (kern, kern_end + 1)
     r["update entry"] = (up, u[0])
     for k, n in enumerate(names):
         r[n] = (u[k], u[k + 1])
-    r["debug + form choice"] = (u[10], u[10] + 160)
+    r["debug + form choice"] = (u[10], up_end + 1)
     r["stance: legs, W"] = (sr, s19)
     r["stance: S"] = (s19, s20)
     r["stance: S^-1"] = (s20, s12)
@@ -62,12 +72,15 @@ def stage_ranges(src):
     return r
 
 
-def main():
-    path = sys.argv[1]
-    src_path = sys.argv[2] if len(sys.argv) > 2 else "quadrupedwholebodycontroller_amd/csrc/wbc_kernel.hip"
-    ranges = stage_ranges(open(src_path).read())
-    lines = open(path).read().split("\n")
-    st = [i for i, l in enumerate(lines) if l.startswith(SYM + ":")][0]
+def stage_table(listing, src, sym=SYM):
+    """Stage name -> Counter(instr, valu, lds, waitcnt, dpp, ...) of kernel `sym` in the listing text,
+    in the stages' order ("?": instructions before the first wbc_kernel.hip line of any stage)."""
+    ranges = stage_ranges(src)
+    lines = listing.split("\n")
+    starts = [i for i, l in enumerate(lines) if l.startswith(sym + ":")]
+    if not starts:
+        raise KeyError(f"no kernel {sym} in the listing (see --sym)")
+    st = starts[0]
     en = [i for i, l in enumerate(lines[st:]) if l.startswith(".Lfunc_end")][0] + st
     files = {}
     for l in lines:
@@ -80,7 +93,7 @@ def main():
         m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", l)
         if m:
             f, ln = int(m.group(1)), int(m.group(2))
-            if "wbc_kernel" in files.get(f, ""):
+            if files.get(f, "").endswith("wbc_kernel.hip"):
                 for n, (a, b) in ranges.items():
                     if a <= ln < b:
                         cur = n
@@ -105,10 +118,28 @@ def main():
             c["s_nop"] += 1
         if t.startswith(("global_", "buffer_", "flat_", "scratch_")):
             c["vmem"] += 1
-    order = list(ranges) + ["?"]
-    for n in order:
+    out = collections.OrderedDict()
+    for n in list(ranges) + ["?"]:
         if n in acc:
-            print("%-28s %s" % (n, dict(acc[n])))
+            out[n] = acc[n]
+    return out
+
+
+def main():
+    argv = sys.argv[1:]
+    sym = SYM
+    if "--sym" in argv:
+        k = argv.index("--sym")
+        sym = argv[k + 1]
+        del argv[k:k + 2]
+    path = argv[0] if argv else os.path.join(CSRC, "build", "wbc_kernel_stance.s")
+    src_path = argv[1] if len(argv) > 1 else os.path.join(CSRC, "wbc_kernel.hip")
+    table = stage_table(open(path).read(), open(src_path).read(), sym)
+    total = collections.Counter()
+    for n, c in table.items():
+        total.update(c)
+        print("%-28s %s" % (n, dict(c)))
+    print("%-28s %s" % ("total", dict(total)))
 
 
 if __name__ == "__main__":

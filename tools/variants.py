@@ -1,5 +1,6 @@
-"""Time the occupancy variants (libwbc_hip_w{N}.so) side by side; each in its own process.
-Usage (GPU box): python tools/variants.py [steps]"""
+"""Time library variants (libwbc_hip_<name>.so: the occupancy variants w{N}, or any A/B pair) side
+by side in interleaved passes; each run in its own process.
+Usage (GPU box): python tools/variants.py [steps] [name,name,...] [passes]"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
@@ -50,8 +51,8 @@ print(json.dumps(res))
 ''' % ROOT
 steps = sys.argv[1] if len(sys.argv) > 1 else "30"
 names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["w2", "w3", "w4", "w5"]
-out = {}
-for rep in range(2):  # two passes, interleaved, to expose box-to-box / run-to-run drift
+passes = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+for rep in range(passes):  # interleaved passes, to expose box-to-box / run-to-run drift
     for n in names:
         lib = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", f"libwbc_hip_{n}.so")
         r = subprocess.run([sys.executable, "-c", CHILD, steps], env=dict(os.environ, WBC_LIB=lib), capture_output=True,
