@@ -20,7 +20,7 @@ import margins as M
 import pytest
 
 import wbc_ref as R
-from quadrupedwholebodycontroller_amd import STATELESS, Engine, workloads
+from quadrupedwholebodycontroller_amd import DEBUG, STATELESS, Engine, split_debug, workloads
 
 pytestmark = pytest.mark.gpu
 
@@ -65,9 +65,15 @@ def test_stateful_trajectory_golden(name):
     for t in range(T):
         e.set_state(g["in_base_pose"][t], g["in_nu"][t], g["in_qj"][t])
         e.set_reference(g["in_ref"][t], g["in_contacts"][t], g["in_switching"][t])
-        e.step(0)
+        e.step(DEBUG)
         o = e.outputs()
         assert np.array_equal(o["status"], g["out_status"][t]), t
+        for j, rec in enumerate(e.debug()):  # the stateful intermediates, feasible or not
+            d = split_debug(rec)
+            for k, a, b in (("bbar", d["bbar"][6:], g["out_bbar"][t, j][6:]), ("r1", d["r1"], g["out_r1"][t, j]),
+                            ("rsw", d["rsw"], g["out_rsw"][t, j])):
+                err = np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b)))
+                assert M.record(k, err, M.STATEFUL_INTERMEDIATE[k]) <= M.STATEFUL_INTERMEDIATE[k], (t, j, k)
         for j in range(nr):
             if g["out_status"][t, j] == 0:
                 assert close_to(o["x"][j], g["out_x"][t, j], M.X, "x"), (t, j, "x")
@@ -257,11 +263,11 @@ def test_long_trot_no_drift_vs_c_oracle():
     oracle's stateful robots (the REDUCED method: the same 12-variable form and hotstart): status and
     iteration counts equal at every cycle, tau at the parity tolerance at every cycle.  The integral
     error e_int and the finite-difference history accumulate over the whole run, so a bias in either
-    would grow here."""
+    would grow here: the worst error of the last 200 cycles is at most 10 x that of the first 200."""
     B, steps = 64, 2000
     robots = R.Robots(np.arange(B), method=R.REDUCED)
     e = Engine(B)
-    worst = 0.0
+    err = np.zeros(steps)
     for t, inp in enumerate(workloads.trot_sequence(B, steps=steps, seed=24)):
         e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
         e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
@@ -271,7 +277,11 @@ def test_long_trot_no_drift_vs_c_oracle():
         assert np.array_equal(o["status"], r["status"]) and np.array_equal(o["iters"], r["iters"]), t
         ok = r["status"] == 0
         assert close_to(o["tau"][ok], r["tau"][ok], M.TAU, "tau"), t
-        worst = max(worst, M.norm_err(o["tau"][ok], r["tau"][ok]))
+        err[t] = M.norm_err(o["tau"][ok], r["tau"][ok])
     e.close()
-    # the error at the end of the run is no larger than the bound either (no growth with time)
-    assert worst <= M.TAU
+    # no growth with time: the worst error of the last 200 cycles against that of the first 200 (both
+    # spans hold two contact switches), with a floor of a few ulps so that two noise-level numbers
+    # cannot fail it
+    early = M.record("tau, first 200 cycles", err[:200].max(), M.TAU)
+    late = M.record("tau, last 200 cycles", err[-200:].max(), M.TAU)
+    assert late <= max(10.0 * early, M.BITS), (early, late)
