@@ -289,6 +289,42 @@ int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table);
  * values broadcast to B rows.  Column 9 is written as 0. */
 int32_t wbc_get_robot_params(wbc_engine* h, double* table);
 
+/* Per-robot ground normals at the feet (sloped and rough terrain): a table of doubles, row-major
+ * [B][WBC_CN_LEN], row b for robot b: the contact normal at each foot in the world frame, legs in
+ * footContacts_ order (LH, LF, RF, RH), three doubles per foot.  Rows are 96 bytes, so a table that
+ * starts 16-byte aligned keeps every row 16-byte aligned (required of a device-bound table).  For
+ * foot l with normal m the friction pyramid of the QP (cpp:404-424) stands on the frame
+ *     n = m / |m|,   t1 = (e_x - (e_x . n) n) / |...|,   t2 = n x t1
+ * and its four faces are, in the reference's order and with bounds (-inf, 0],
+ *     t1 - mu n,   -(t1 + mu n),   t2 - mu n,   -(t2 + mu n);
+ * m = (0, 0, c), c > 0, gives exactly the flat-ground rows.  The forces of the QP are world-frame, so
+ * nothing else of the problem changes.  A foot's normal is valid when its entries are finite,
+ * 0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5 (slopes up to 60 degrees); swing feet are validated too. */
+enum { WBC_CN_LEN = 12 };
+/* Host table, validated and then copied on the engine stream (the call synchronizes it, so the
+ * caller may reuse the array).  An invalid foot returns WBC_ERR_ARG, wbc_last_error names the row
+ * and the foot, and the table in force before the call stays in force.  NULL clears the table: back
+ * to flat ground.
+ * While normals are in force (this table or a device-bound one), with or without a robot-parameter
+ * table:
+ *  - supported: wbc_step in its default form (stateless, stateful and WBC_COLD; with WBC_DEBUG,
+ *    WBC_NO_X, WBC_TIMED and WBC_GROUP) and plain wbc_cycle.  Normals may change between stateful
+ *    cycles; history and hotstart carry over (a warm set that no longer fits is rejected by the
+ *    hotstart's own check, and the solve starts cold).
+ *  - refused with WBC_ERR_STATE (wbc_last_error names the call or flag): wbc_update, wbc_solve,
+ *    wbc_step_modes, and wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT.  These
+ *    forms stand on flat ground only; they run as before once the normals are cleared
+ *    (wbc_set_contact_normals(h, NULL) and no device table bound). */
+int32_t wbc_set_contact_normals(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_CN_LEN] (no copy, no host validation; the step reads the pointer
+ * directly).  NULL restores the engine-owned table of wbc_set_contact_normals, or none if none was
+ * set.  On the device a row with an invalid foot gives that robot WBC_QP_NUMERIC and zero outputs,
+ * as a non-finite input does; no other robot is touched. */
+int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_CN_LEN] to the host as given (synchronous); without one, (0, 0, 1)
+ * for every foot. */
+int32_t wbc_get_contact_normals(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

@@ -5,7 +5,9 @@ computeJointTorques, src/whole_body_controller.cpp:650-652) as hand-written HIP 
 behind the C-ABI in include/wbc.h.  This package is the Python view of that C-ABI:
 
   Engine          batched handle (wbc_create ... wbc_get_output), see _capi.py; per-robot controller
-                  parameters: Engine.set_robot_params / bind_device_robot_params / robot_params
+                  parameters: Engine.set_robot_params / bind_device_robot_params / robot_params;
+                  per-robot ground normals at the feet (sloped ground): Engine.set_contact_normals /
+                  bind_device_contact_normals / contact_normals
   Planner         batched motion planner (WbcReferenceMsg producer), see _capi.py
   workloads       synthetic inputs of the BASELINE.json configurations
   sharding        robot shards and the per-step all-gather of the multi-GPU path
@@ -18,8 +20,8 @@ The product path has no CPU fallback: without libwbc_hip.so or a GPU it raises.
 """
 from ._capi import (COLD, DEBUG, FUSED, GROUP, NO_X, RESIDENT, SPLIT, STATELESS, TIMED, QP_INFEASIBLE, QP_MAX_ITER, QP_NUMERIC, QP_OK, Engine, WbcError,  # noqa: F401
                     WbcModel, WbcParams, anymal_model, default_params, load_library, model_from_urdf, split_debug, Planner,
-                    WbcPlannerParams, ROBOT_PARAM_NAMES, robot_param_table)
+                    WbcPlannerParams, ROBOT_PARAM_NAMES, robot_param_table, contact_normal_table)
 
 __all__ = ["Engine", "Planner", "WbcPlannerParams", "model_from_urdf", "WbcError", "WbcModel", "WbcParams", "anymal_model", "default_params", "load_library",
            "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC",
-           "ROBOT_PARAM_NAMES", "robot_param_table"]
+           "ROBOT_PARAM_NAMES", "robot_param_table", "contact_normal_table"]

@@ -20,6 +20,9 @@ QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
 # columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
 ROBOT_PARAM_NAMES = ("friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing", "slack_weight")
 RP_LEN = 10
+# the per-robot contact-normal table (WBC_CN_LEN in include/wbc.h): three doubles per foot, legs LH, LF, RF, RH
+CN_LEN = 12
+FOOT_NAMES = ("LH", "LF", "RF", "RH")
 
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
@@ -31,6 +34,7 @@ C_API_SYMBOLS = [
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
     "wbc_last_error", "wbc_model_from_urdf", "wbc_set_robot_params", "wbc_bind_device_robot_params", "wbc_get_robot_params",
+    "wbc_set_contact_normals", "wbc_bind_device_contact_normals", "wbc_get_contact_normals",
 ]
 
 
@@ -102,10 +106,14 @@ def load_library(path: str = LIB_PATH):
         "wbc_set_robot_params": ([P, P], I32),
         "wbc_bind_device_robot_params": ([P, P], I32),
         "wbc_get_robot_params": ([P, P], I32),
+        "wbc_set_contact_normals": ([P, P], I32),
+        "wbc_bind_device_contact_normals": ([P, P], I32),
+        "wbc_get_contact_normals": ([P, P], I32),
     }
     for name, (argt, rest) in sig.items():
         if name in ("wbc_modes_per_wave", "wbc_set_robot_params", "wbc_bind_device_robot_params",
-                    "wbc_get_robot_params") and not hasattr(lib, name):
+                    "wbc_get_robot_params", "wbc_set_contact_normals", "wbc_bind_device_contact_normals",
+                    "wbc_get_contact_normals") and not hasattr(lib, name):
             continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -176,6 +184,31 @@ def robot_param_table(batch: int, params: WbcParams, table) -> np.ndarray:
     return out
 
 
+def contact_normal_table(batch: int, normals) -> np.ndarray:
+    """The [B, CN_LEN] table of wbc_set_contact_normals from a (B, 12) or (B, 4, 3) array (row b: the
+    ground normal at each foot of robot b, world frame, legs LH, LF, RF, RH), or from one (3,) normal or
+    one (4, 3) set of four, broadcast to all robots.  Validated as the engine validates it (finite,
+    0.25 <= |m|^2 <= 4, m_z / |m| >= 0.5); ValueError names the row and the foot."""
+    B = int(batch)
+    t = np.asarray(normals, np.float64)
+    if t.shape == (3,):
+        t = np.broadcast_to(t, (B, 4, 3))
+    elif t.shape == (4, 3):
+        t = np.broadcast_to(t, (B, 4, 3))
+    elif t.shape == (B, CN_LEN):
+        t = t.reshape(B, 4, 3)
+    elif t.shape != (B, 4, 3):
+        raise ValueError(f"contact normals: need shape ({B}, {CN_LEN}), ({B}, 4, 3), (4, 3) or (3,), got {t.shape}")
+    s = (t * t).sum(axis=2)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(t).all(axis=2) & (s >= 0.25) & (s <= 4.0) & (t[:, :, 2] > 0.0) & (4.0 * t[:, :, 2] ** 2 >= s)
+    if not ok.all():
+        b, l = (int(v) for v in np.argwhere(~ok)[0])
+        raise ValueError(f"contact normals: row {b}, foot {l} ({FOOT_NAMES[l]}) = {tuple(t[b, l])}: need finite entries, "
+                         "0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5")
+    return np.ascontiguousarray(t.reshape(B, CN_LEN))
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -185,6 +218,7 @@ class Engine:
         self.n_modes = 0
         self._stream = None  # the bound caller stream object (kept alive while bound)
         self._rp_table = None  # the bound device table's owner (kept alive while bound)
+        self._cn_table = None  # the same for the bound contact-normal table
         self.params = WbcParams.from_buffer_copy(params) if params else default_params()  # the engine-wide wbc_params
         self.h = C.c_void_p()
         rc = self.lib.wbc_create(C.byref(model) if model else None, C.byref(params) if params else None,
@@ -201,6 +235,7 @@ class Engine:
             self.h = C.c_void_p()
         self._stream = None
         self._rp_table = None
+        self._cn_table = None
 
     def __del__(self):
         try:
@@ -257,6 +292,28 @@ class Engine:
         """wbc_get_robot_params: the [B, 10] table in force (without one: the engine-wide values in B rows)."""
         out = np.zeros((self.batch, RP_LEN))
         self._check(self.lib.wbc_get_robot_params(self.h, _ptr(out)), "wbc_get_robot_params")
+        return out
+
+    def set_contact_normals(self, normals):
+        """wbc_set_contact_normals: the ground normal at each foot of each robot (sloped ground) for the
+        default step.  `normals`: a (B, 12) or (B, 4, 3) array, or one (3,) normal / one (4, 3) set
+        broadcast to all robots (contact_normal_table); None clears the table: flat ground."""
+        t = None if normals is None else contact_normal_table(self.batch, normals)
+        self._check(self.lib.wbc_set_contact_normals(self.h, _ptr(t)), "wbc_set_contact_normals")
+
+    def bind_device_contact_normals(self, table=0):
+        """wbc_bind_device_contact_normals: a caller-owned device table [B, 12] of doubles (no copy, no
+        host validation): an integer device pointer, or an object with data_ptr() (a torch tensor), which
+        the engine keeps referenced while it is bound.  0 / None: the engine-owned table, or none."""
+        ptr = int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table or 0)
+        self._check(self.lib.wbc_bind_device_contact_normals(self.h, C.c_void_p(ptr) if ptr else None),
+                    "wbc_bind_device_contact_normals")
+        self._cn_table = table if ptr else None
+
+    def contact_normals(self) -> np.ndarray:
+        """wbc_get_contact_normals: the [B, 12] table in force (without one: (0, 0, 1) for every foot)."""
+        out = np.zeros((self.batch, CN_LEN))
+        self._check(self.lib.wbc_get_contact_normals(self.h, _ptr(out)), "wbc_get_contact_normals")
         return out
 
     def set_stream(self, stream):

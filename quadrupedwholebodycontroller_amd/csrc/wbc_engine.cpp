@@ -12,6 +12,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "wbc.h"
 #include "wbc_anymal_model.h"
@@ -27,6 +28,9 @@ extern "C" hipError_t wbc_launch_stance_step(const wbc::KernelArgs* a, hipStream
 extern "C" hipError_t wbc_launch_update_solve_rp0(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_cn0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_cn1(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_stance_step_cn(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
@@ -65,6 +69,15 @@ struct wbc_engine {
     bool rp_own = false;
     const double* rp_bound = nullptr;
     const double* in_rp = nullptr;
+    // per-robot ground normals at the feet (KernelArgs::cn, [B][WBC_CN_LEN]), held as the parameter
+    // table is: the engine's own table, a caller's device table, the one in force.  The kernels that
+    // read them are per-robot-parameter instances, so without a parameter table in force the step
+    // reads d_rp_uni: the engine-wide params in B rows (built at the first use; params never change)
+    double* d_cn = nullptr;
+    bool cn_own = false;
+    const double* cn_bound = nullptr;
+    const double* in_cn = nullptr;
+    double* d_rp_uni = nullptr;
     // owned inputs: one device block [pose | nu | qj | ref | contacts | switching] (so a host cycle
     // is one H2D copy), and the outputs one block [tau | grf | status | iters | x]
     void* d_inblk = nullptr;
@@ -174,7 +187,8 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) {
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    a.rp = h->in_rp;
+    a.rp = h->in_rp ? h->in_rp : (h->in_cn ? h->d_rp_uni : nullptr);
+    a.cn = h->in_cn;
     a.base_pose = h->in_pose;
     a.nu = h->in_nu;
     a.qj = h->in_qj;
@@ -539,7 +553,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_box) (void)hipHostFree(h->res_box);
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
-                    h->d_fb, h->d_dbg, h->d_qmap, h->d_rp};
+                    h->d_fb, h->d_dbg, h->d_qmap, h->d_rp, h->d_cn, h->d_rp_uni};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -676,6 +690,83 @@ int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
     return WBC_OK;
 }
 
+// the uniform parameter table the contact-normal kernels read when no parameter table is in force
+static int32_t ensure_rp_uniform(wbc_engine* h) {
+    if (h->d_rp_uni) return WBC_OK;
+    const size_t B = (size_t)h->batch;
+    const wbc_params& p = h->params;
+    const double row[WBC_RP_LEN] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight, 0.0};
+    std::vector<double> t(B * WBC_RP_LEN);
+    for (size_t b = 0; b < B; ++b) std::memcpy(t.data() + b * WBC_RP_LEN, row, sizeof(row));
+    WBC_HIP(hipSetDevice(h->device));
+    double* d = nullptr;
+    if (dalloc(&d, B * WBC_RP_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_rp_uni");
+    const hipError_t e = hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(WBC_ERR_HIP, std::string("hipMemcpy failed: d_rp_uni: ") + hipGetErrorString(e));
+    }
+    h->d_rp_uni = d;
+    return WBC_OK;
+}
+
+int32_t wbc_set_contact_normals(wbc_engine* h, const double* table) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (!table) {  // back to flat ground (or to a caller's bound table)
+        h->cn_own = false;
+        h->in_cn = h->cn_bound;
+        return WBC_OK;
+    }
+    static const char* const feet[WBC_NUM_LEGS] = {"LH", "LF", "RF", "RH"};
+    const size_t B = (size_t)h->batch;
+    for (size_t b = 0; b < B; ++b) {
+        const int l = wbc::cn_bad_foot(table + b * WBC_CN_LEN);
+        if (l >= 0) {
+            const double* m = table + b * WBC_CN_LEN + 3 * l;
+            char val[96];
+            std::snprintf(val, sizeof(val), "(%g, %g, %g)", m[0], m[1], m[2]);
+            return fail(WBC_ERR_ARG, "wbc_set_contact_normals: row " + std::to_string(b) + ", foot " + std::to_string(l) + " (" +
+                                         feet[l] + ") = " + val +
+                                         ": need finite entries, 0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5");
+        }
+    }
+    WBC_HIP(sync_own(h));
+    if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    WBC_HIP(hipSetDevice(h->device));
+    if (!h->d_cn && dalloc(&h->d_cn, B * WBC_CN_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_cn");
+    WBC_HIP(hipMemcpyAsync(h->d_cn, table, B * WBC_CN_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));  // the host table may be reused by the caller
+    h->cn_own = true;
+    if (!h->cn_bound) h->in_cn = h->d_cn;
+    return WBC_OK;
+}
+
+int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
+        return fail(WBC_ERR_ARG, "wbc_bind_device_contact_normals: the table must be 16-byte aligned");
+    if (d_table) {
+        if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    }
+    h->cn_bound = d_table;
+    h->in_cn = d_table ? d_table : (h->cn_own ? h->d_cn : nullptr);
+    return WBC_OK;
+}
+
+int32_t wbc_get_contact_normals(wbc_engine* h, double* table) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    const size_t B = (size_t)h->batch;
+    if (h->in_cn) {
+        WBC_HIP(sync_own(h));
+        WBC_HIP(hipSetDevice(h->device));
+        WBC_HIP(hipMemcpyAsync(table, h->in_cn, B * WBC_CN_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        WBC_HIP(hipStreamSynchronize(h->stream));
+    } else {
+        for (size_t e = 0; e < B * WBC_CN_LEN; ++e) table[e] = (e % 3 == 2) ? 1.0 : 0.0;
+    }
+    return WBC_OK;
+}
+
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
@@ -696,6 +787,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_update: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
+    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_update: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -709,6 +801,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_solve: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_solve: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
+    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_solve: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
@@ -724,6 +817,10 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
         return fail(WBC_ERR_STATE, std::string("wbc_step: ") + ((flags & WBC_SPLIT) ? "WBC_SPLIT" : "WBC_FUSED") +
                                        " with a per-robot parameter table in force (default form only; clear it with "
                                        "wbc_set_robot_params(h, NULL))");
+    if (h->in_cn && (flags & (WBC_SPLIT | WBC_FUSED)))
+        return fail(WBC_ERR_STATE, std::string("wbc_step: ") + ((flags & WBC_SPLIT) ? "WBC_SPLIT" : "WBC_FUSED") +
+                                       " with contact normals in force (default form only; clear them with "
+                                       "wbc_set_contact_normals(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
@@ -742,7 +839,12 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
         // a per-robot parameter table in force: the same three choices among its own instances
         // (wbc_kernel_rps.hip stance-only, wbc_kernel_rp0.hip stateless, wbc_kernel_rp1.hip stateful)
         WBC_HIP(begin_step16(h, a, flags));
-        if (a.rp && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_rp(&a, h->stream));
+        // contact normals in force: their instances (wbc_kernel_cns.hip, wbc_kernel_cn0.hip,
+        // wbc_kernel_cn1.hip), which read the parameter table too (the caller's, or the
+        // engine's uniform one)
+        if (a.cn && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_cn(&a, h->stream));
+        else if (a.cn) WBC_HIP(a.stateful ? wbc_launch_update_solve_cn1(&a, h->stream) : wbc_launch_update_solve_cn0(&a, h->stream));
+        else if (a.rp && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_rp(&a, h->stream));
         else if (a.rp) WBC_HIP(a.stateful ? wbc_launch_update_solve_rp1(&a, h->stream) : wbc_launch_update_solve_rp0(&a, h->stream));
         else if (step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step(&a, h->stream));
         else WBC_HIP(wbc_launch_update_solve(&a, h->stream));
@@ -783,6 +885,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     WBC_HIP(sync_own(h));
     if (!h->n_modes) return fail(WBC_ERR_STATE, "wbc_step_modes: no mode hypotheses set (wbc_set_modes)");
     if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_step_modes: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
+    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_step_modes: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
     WBC_HIP(hipSetDevice(h->device));
@@ -963,6 +1066,11 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
                                        ((flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT") +
                                        " with a per-robot parameter table in force (plain cycle only; clear it with "
                                        "wbc_set_robot_params(h, NULL))");
+    if (h->in_cn && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
+        return fail(WBC_ERR_STATE, std::string("wbc_cycle: ") +
+                                       ((flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT") +
+                                       " with contact normals in force (plain cycle only; clear them with "
+                                       "wbc_set_contact_normals(h, NULL))");
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     const size_t inb = in_block_bytes(B), outb = out_block_bytes(B);

@@ -1746,10 +1746,21 @@ __device__ __forceinline__ double fric_elem(double tv, bool frc, int leg, int k,
     }
     return tv;
 }
-template <bool ROWS, bool GEN, int STF = -1, bool RP = false>
+// CN (the contact-normal instances, KernelArgs::cn): cnf holds the three non-zero entries of the
+// lane's own friction face, built from its foot's frame (cn_face_elem); the shared table is not read.
+// Another row's face comes from its owner lane's registers (face p lives in lane p & 15): three
+// segment shuffles.  In the pass its dot with column i of J reads the three entries of the column at
+// the face's leg instead of selecting the face into a 12-vector; the sums are those of the 12-long
+// form with zeros, so flat normals give the plain step's bits.
+template <bool CN>
+__device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = CN ? seg_shfl(cnf[r], p & 15) : 0.0;
+}
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
-                        double hws_tag = 0.0) {
+                        double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr) {
     constexpr int N = 12;
     constexpr int NTS = GEN ? 12 : NTS_ST;  // Nt row stride
     const wbc_params& pr = a.pv;
@@ -1770,7 +1781,8 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
         const int r = m % 3;
         const double fv = (r == 0) ? ((rr == 0) ? -1.0 : (rr == 1 ? 1.0 : 0.0))
                         : (r == 1) ? ((rr == 2) ? -1.0 : (rr == 3 ? 1.0 : 0.0)) : pr.friction;
-        n0[m] = (m / 3 == fl) ? fv : 0.0;
+        if constexpr (CN) n0[m] = (m / 3 == fl) ? cnf[r] : 0.0;
+        else n0[m] = (m / 3 == fl) ? fv : 0.0;
         n1[m] = -sg * V.Nt[k1 * NTS + m];
         const double nt2 = V.Nt[k2 * NTS + m];  // (k2 is a valid row in every lane: loaded, then masked)
         n2[m] = v2 ? -sg * nt2 : 0.0;
@@ -1938,6 +1950,16 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double* nrow = V.Nt + (frc ? fo : to);
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     nn = 0.0;
+                    if constexpr (CN) {
+                        double e[3];
+                        cn_face<CN>(cnf, p, e);
+#pragma unroll
+                        for (int k = 0; k < N; ++k) {
+                            np[k] = frc ? ((k / 3 == ((p & 15) >> 2)) ? e[k % 3] : 0.0) : sgn * V.Nt[to + k];
+                            nn = fma(np[k], np[k], nn);
+                        }
+                        return;
+                    }
 #pragma unroll
                     for (int k = 0; k < N; ++k) {
                         np[k] = sgn * fric_elem<RP>(nrow[k], frc, (p & 15) >> 2, k, pr.friction);
@@ -2027,10 +2049,21 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double* nrow = frc ? &V.fric[FRIC_ROW(p)] : &V.Nt[(tq >> 1) * NTS];
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     double np[N], nn = 0.0;
+                    if constexpr (CN) {
+                        double e[3];
+                        cn_face<CN>(cnf, p, e);
+                        const double* trow = &V.Nt[(tq >> 1) * NTS];
 #pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        np[k] = sgn * fric_elem<RP>(nrow[k], frc, (p & 15) >> 2, k, pr.friction);
-                        nn = fma(np[k], np[k], nn);
+                        for (int k = 0; k < N; ++k) {
+                            np[k] = frc ? ((k / 3 == ((p & 15) >> 2)) ? e[k % 3] : 0.0) : sgn * trow[k];
+                            nn = fma(np[k], np[k], nn);
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < N; ++k) {
+                            np[k] = sgn * fric_elem<RP>(nrow[k], frc, (p & 15) >> 2, k, pr.friction);
+                            nn = fma(np[k], np[k], nn);
+                        }
                     }
                     double d2[N], rk, zn, zk, dq, jq;
                     direction(dot_col(jc, np), pos, d2, rk, zn, zk, dq, jq);
@@ -2142,10 +2175,26 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                 // two chains per dot in the pass (not four: the pass is issue-bound, and each
                 // dot then ends in one add instead of three)
                 double a2[2] = {0.0, 0.0};
+                double dn;
+                if constexpr (CN) {
+                    // a friction face: its three entries from the owner lane, against the column's
+                    // three entries at the face's leg (a 12-long dot with nine zeros, term for term);
+                    // a torque row: the row of Nt as before
+                    double e[3];
+                    cn_face<CN>(cnf, pstar, e);
+                    const double* jf = &Jl[3 * ((pstar & 15) >> 2) * JMS + i];
+                    const double j0 = jf[0], j1 = jf[JMS], j2 = jf[2 * JMS];
+                    const double* trow = V.Nt + (frc ? 0 : to);
 #pragma unroll
-                for (int k = 0; k < N; ++k)
-                    a2[k & 1] = fma(jc[k], fric_elem<RP>(nrow[k], frc, (pstar & 15) >> 2, k, pr.friction), a2[k & 1]);
-                const double dn = a2[0] + a2[1];
+                    for (int k = 0; k < N; ++k) a2[k & 1] = fma(jc[k], trow[k], a2[k & 1]);
+                    const double df = fma(j2, e[2], fma(j0, e[0], 0.0)) + fma(j1, e[1], 0.0);
+                    dn = frc ? df : a2[0] + a2[1];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < N; ++k)
+                        a2[k & 1] = fma(jc[k], fric_elem<RP>(nrow[k], frc, (pstar & 15) >> 2, k, pr.friction), a2[k & 1]);
+                    dn = a2[0] + a2[1];
+                }
                 dj = ((l < N) ? ((frc || (tq & 1)) ? 1.0 : -1.0) : 0.0) * dn;
             }
             const double sps = seg_shfl(sel3d(js, sp0, sp1, sp2), ol);
@@ -2214,7 +2263,13 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                         if (k >= l1 && k < q) {
                             const int pl = seg_shfl_i(act, k);
                             double nl;  // component i of row pl's normal
-                            if (pl < 16) {
+                            if constexpr (CN) {
+                                double e[3];
+                                cn_face<CN>(cnf, pl < 0 ? 0 : pl, e);
+                                const int qt = pl < 16 ? 0 : pl - 16;
+                                const double tn = ((qt & 1) ? 1.0 : -1.0) * V.Nt[(qt >> 1) * NTS + i];
+                                nl = (pl < 16) ? ((i / 3 == (pl >> 2)) ? sel3(e, i % 3) : 0.0) : tn;
+                            } else if (pl < 16) {
                                 const int rp = pl & 3, r = i % 3;
                                 const double fv = (r == 0) ? ((rp == 0) ? -1.0 : (rp == 1 ? 1.0 : 0.0))
                                                 : (r == 1) ? ((rp == 2) ? -1.0 : (rp == 3 ? 1.0 : 0.0)) : pr.friction;
@@ -2390,10 +2445,11 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false>
+          bool RP = false, bool CN = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
-                             const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr) {
+                             const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
+                             [[maybe_unused]] const double* cnf = nullptr) {
     const wbc_params& pr = a.pv;
     const bool switching = a.switching[rb] != 0;
     const bool stateful = STF < 0 ? a.stateful != 0 : STF == 1;  // (STF: as solve16's)
@@ -3233,7 +3289,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             double hrow[12], gsv = 0.0;
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
-                solve16<true, false, STF, RP>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK);
+                solve16<true, false, STF, RP, CN>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf);
                 return true;
             }
             return false;
@@ -3243,8 +3299,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         bool vac = false;
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
-            solve16<true, true, STF, RP>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi,
-                                         hWtag);
+            solve16<true, true, STF, RP, CN>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi,
+                                             hWtag, cnf);
             return true;
         }
         return false;
@@ -3323,8 +3379,12 @@ __device__ __forceinline__ int nth_leg(int kap, int idx, int want) {
 //   R2  friction pyramid  -D_rr f_l >= 0                                          (cpp:404-424)
 //   R3  torque limits     +-(Mbar_j qdd - Jc_j^T f) >= -tau_max -+ bbar_j          (cpp:495,506,513)
 //   R4/R5 swing rows      +-(Js_j qdd + Js_com a) + s >= +-c'                     (cpp:496-497,507-515)
+// CN: cn is the QP's row of KernelArgs::cn, and a friction face stands on its foot's own frame
+// (cn_frame; a foot the step does not accept stands on flat ground: its robot is flagged)
+template <bool CN = false>
 __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& mp, const wbc_params& pr, int p,
-                             double* n, double& b, bool& is_eq, double& nsel, double& tolv) {
+                             double* n, double& b, bool& is_eq, double& nsel, double& tolv,
+                             [[maybe_unused]] const double* cn = nullptr) {
     const int kap = mp.kap;
     const int t_fr = mp.neq, t_tq = mp.neq + mp.nfr, t_sw = t_tq + mp.ntq;
     const bool in = p < mp.m;
@@ -3350,6 +3410,12 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
     const double scp = eq ? 1.0 : (sw ? sg : 0.0);
     const double stq = tq ? -sg : 0.0;
     const double* grow = G[3 * l + k];
+    [[maybe_unused]] double cnn[3], ct1[3], ct2[3];
+    if constexpr (CN) {
+        const double cm[3] = {cn[3 * l], cn[3 * l + 1], cn[3 * l + 2]};
+        const double flat[3] = {0.0, 0.0, 1.0};
+        cn_frame(cn_valid(cm) ? cm : flat, cnn, ct1, ct2);
+    }
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) {
         const bool st = (kap >> mm) & 1;
@@ -3359,7 +3425,11 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
             // friction face rr of stance leg l: (-1 | 1 | 0, 0 | 0 | -1 | 1, mu)
             const double fv = (r == 0) ? ((rr == 0) ? -1.0 : (rr == 1 ? 1.0 : 0.0))
                             : (r == 1) ? ((rr == 2) ? -1.0 : (rr == 3 ? 1.0 : 0.0)) : pr.friction;
-            if (fr && mm == l) x = fv;
+            if constexpr (CN) {
+                if (fr && mm == l) x = cn_face_elem(cnn, ct1, ct2, pr.friction, rr, r);
+            } else {
+                if (fr && mm == l) x = fv;
+            }
             if (sw && mm == l && r == k) x = 1.0;  // the slack of swing leg l
             n[12 + 3 * mm + r] = x;
         }
@@ -3585,6 +3655,7 @@ constexpr int PRE_FLAG = 90;  // packed index of Presolve::presolved
 static_assert(offsetof(Presolve, presolved) == PRE_FLAG * sizeof(double), "PRE_FLAG");
 static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing");
 
+template <bool CN = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
@@ -3639,7 +3710,8 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
     {
         EST(a, rb, 5);
         double nsel;
-        build_normal(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv);
+        if constexpr (CN) build_normal<true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN);
+        else build_normal(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv);
         EST(a, rb, 6);
         double np[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -4508,7 +4580,8 @@ struct SolveLds {
 // wbc_kernel_modes.hip) include this file under their own macro, which keeps only their kernel and
 // its launcher; this file's own unit builds everything else
 #if defined(WBC_STANCE_TU) || defined(WBC_STEP0_TU) || defined(WBC_STEP1_TU) || defined(WBC_MODES_TU) || \
-    defined(WBC_RESIDENT_TU) || defined(WBC_RP0_TU) || defined(WBC_RP1_TU) || defined(WBC_RPS_TU)
+    defined(WBC_RESIDENT_TU) || defined(WBC_RP0_TU) || defined(WBC_RP1_TU) || defined(WBC_RPS_TU) || \
+    defined(WBC_CN0_TU) || defined(WBC_CN1_TU) || defined(WBC_CNS_TU)
 #define WBC_SINGLE_TU 1
 #endif
 #ifndef WBC_SINGLE_TU
@@ -4611,6 +4684,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
+template <bool CN = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -4632,7 +4706,8 @@ __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base,
     pv.slack_weight = bad ? base.slack_weight : r[WBC_RP_SLACK_WEIGHT];
 }
 // (TAG >= 6: the per-robot-parameter instances, KernelArgs::rp: each fallback QP is solved under its
-// own robot's row, as its reduction was attempted)
+// own robot's row, as its reduction was attempted; TAG >= 10: the contact-normal instances, which
+// build the fallback QP's friction faces from its own row of KernelArgs::cn as well, build_normal<true>)
 template <int TAG>
 __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, unsigned long long fm, int qp,
                                                           SolveLds* L) {
@@ -4651,7 +4726,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
-        solve_general_qp(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        solve_general_qp<(TAG >= 10)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -4668,8 +4743,12 @@ __device__ __forceinline__ int xcd_block(int b, int n) {
 // qp of KernelArgs::rp (indexed by the QP, never by the wave slot: a mapped, padding or
 // empty-workgroup segment reads the row of the QP it computes), the other parameters from
 // KernelArgs::pv.  No mode hypotheses (the launchers refuse).
-template <int STF, bool SONLY = false, bool RP = false>
+// CN (with RP): the contact-normal instances (wbc_kernel_cn0.hip, wbc_kernel_cn1.hip,
+// wbc_kernel_cns.hip): each lane takes its own foot's ground normal (leg lane >> 2) from row qp of
+// KernelArgs::cn, indexed as the parameter row is, and builds its friction face from it.
+template <int STF, bool SONLY = false, bool RP = false, bool CN = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
+    static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
     const int K = a.modes;
@@ -4738,6 +4817,14 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
             rpv[2 * c + 1] = w.y;
         }
     }
+    // the ground normal of the lane's own foot, requested in the same batch (three 8-byte loads: a
+    // foot's 24 bytes are 8-byte aligned)
+    [[maybe_unused]] double cnm[3];
+    if constexpr (CN) {
+        const double* m = a.cn + (size_t)qp * WBC_CN_LEN + 3 * (lane >> 2);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cnm[c] = m[c];
+    }
     // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy
     stage_to_lds<LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
     if (__all(empty)) return;  // the unused tail of a device-built map (uniform)
@@ -4752,6 +4839,20 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
         const bool bad = rp_bad_column(rpv) >= 0;
         rp_apply(ar.pv, a.pv, rpv, bad);
         if (bad) vin[0] = __builtin_nan("");
+        if constexpr (CN) {
+            // the lane's face (leg lane >> 2, face lane & 3) from its foot's frame and the robot's mu;
+            // a robot with a foot the step does not accept is flagged as one with a bad parameter row
+            // is, and stands on flat ground meanwhile
+            const bool cbad = seg_any<UPD_SUB>(!cn_valid(cnm));
+            if (cbad) { cnm[0] = 0.0; cnm[1] = 0.0; cnm[2] = 1.0; }
+            if (cbad) vin[0] = __builtin_nan("");
+            double fn[3], ft1[3], ft2[3], cnf[3];
+            cn_frame(cnm, fn, ft1, ft2);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) cnf[r] = cn_face_elem(fn, ft1, ft2, ar.pv.friction, lane & 3, r);
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true>(
+                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf);
+        } else
         solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true>(ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg],
                                                                                 nullptr, L.model, &L.fric[0], vin);
     } else {
@@ -4775,7 +4876,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<(RP ? 6 : 2) + STF>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<(CN ? 10 : RP ? 6 : 2) + STF>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -4939,6 +5040,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
+template <bool CN>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -4965,6 +5067,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
+template <bool CN>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -4991,7 +5094,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5276,6 +5379,29 @@ extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStr
 extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st) {
     if (a->nwaves <= 0 || !a->stateful || a->modes || !a->rp) return hipErrorInvalidValue;
     hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<1, false, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+#elif defined(WBC_CN0_TU)
+// The default step under per-robot contact normals (KernelArgs::cn, with KernelArgs::rp), stateless,
+// any mask mix, all-stance steps included (wbc_kernel_cn0.hip, Makefile CN0_KFLAGS)
+extern "C" hipError_t wbc_launch_update_solve_cn0(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || a->stateful || a->modes || !a->rp || !a->cn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, false, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+#elif defined(WBC_CNS_TU)
+// The stance-only default step under per-robot contact normals (wbc_kernel_cns.hip, Makefile
+// CNS_KFLAGS): stateless, every mask 15, as wbc_launch_stance_step_rp
+extern "C" hipError_t wbc_launch_stance_step_cn(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || a->stateful || a->modes || a->qmap || !a->rp || !a->cn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, true, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+#elif defined(WBC_CN1_TU)
+// The stateful default step under per-robot contact normals (wbc_kernel_cn1.hip, Makefile CN1_KFLAGS)
+extern "C" hipError_t wbc_launch_update_solve_cn1(const wbc::KernelArgs* a, hipStream_t st) {
+    if (a->nwaves <= 0 || !a->stateful || a->modes || !a->rp || !a->cn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<1, false, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 #else

@@ -1,0 +1,7 @@
+// wbc_kernel_cns.hip — the stance-only default step under per-robot contact normals
+// (wbc_update_solve_kernel<0, true, true, true>, KernelArgs::cn): a stateless step whose
+// QPs all have contact mask 15, the general 12-variable form compiled out, as wbc_kernel_rps.hip.
+// A translation unit of its own (Makefile CNS_KFLAGS); the code is wbc_kernel.hip's, which
+// WBC_CNS_TU limits to this one kernel and its launcher.
+#define WBC_CNS_TU 1
+#include "wbc_kernel.hip"

@@ -192,6 +192,12 @@ struct KernelArgs {
     // wbc_kernel_rp0.hip, wbc_kernel_rp1.hip), which take the nine values of their QP's row in place
     // of pv's.  Last, so that no other argument's offset moves.
     const double* rp;
+    // Per-robot ground normals at the feet (wbc_set_contact_normals / wbc_bind_device_contact_normals):
+    // [batch][WBC_CN_LEN], row qp for QP qp; read only by the contact-normal instances of the default
+    // step (wbc_kernel_cn0.hip, wbc_kernel_cn1.hip), which are per-robot-parameter instances too: the
+    // engine points rp at a uniform table of its own when only normals are in force.  After rp, so
+    // that no other argument's offset moves.
+    const double* cn;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -214,6 +220,38 @@ WBC_HD inline int rp_bad_column(const double* r) {
         if (!__builtin_isfinite(r[c]) || neg) return c;
     }
     return -1;
+}
+// The ground normal m of one foot (three doubles of a wbc.h WBC_CN_LEN row) the step accepts: finite,
+// 0.25 <= |m|^2 <= 4, m_z / |m| >= 0.5.  One definition for the host's validation
+// (wbc_set_contact_normals) and the kernels' (a device-bound row); cn_bad_foot: -1, or the first
+// foot of the row that fails.
+WBC_HD inline bool cn_valid(const double* m) {
+    const double s = m[0] * m[0] + m[1] * m[1] + m[2] * m[2];
+    return s >= 0.25 && s <= 4.0 && m[2] > 0.0 && 4.0 * m[2] * m[2] >= s;  // (a NaN entry fails s >= 0.25)
+}
+WBC_HD inline int cn_bad_foot(const double* row) {
+    for (int l = 0; l < WBC_NUM_LEGS; ++l)
+        if (!cn_valid(row + 3 * l)) return l;
+    return -1;
+}
+// The friction frame of a valid normal m: n = m / |m|, t1 = e_x less its part along n, normalised,
+// t2 = n x t1.  Square root and divisions are the correctly rounded ones (no fast reciprocal), so
+// that m = (0, 0, c) gives exactly (1, 0, 0), (0, 1, 0), (0, 0, 1) and the flat-ground rows.
+WBC_HD inline void cn_frame(const double* m, double* n, double* t1, double* t2) {
+    const double r = __builtin_sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    for (int k = 0; k < 3; ++k) n[k] = m[k] / r;
+    const double u[3] = {1.0 - n[0] * n[0], 0.0 - n[0] * n[1], 0.0 - n[0] * n[2]};
+    const double iq = 1.0 / __builtin_sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    for (int k = 0; k < 3; ++k) t1[k] = u[k] * iq;
+    t2[0] = n[1] * t1[2] - n[2] * t1[1];
+    t2[1] = n[2] * t1[0] - n[0] * t1[2];
+    t2[2] = n[0] * t1[1] - n[1] * t1[0];
+}
+// Entry r of face rr's row for a foot with frame (n, t1, t2) and friction mu, in the engine's sign
+// (row . f >= 0): mu n -+ t1 (rr = 0, 1), mu n -+ t2 (rr = 2, 3); flat ground: (-+1, 0, mu), (0, -+1, mu)
+WBC_HD inline double cn_face_elem(const double* n, const double* t1, const double* t2, double mu, int rr, int r) {
+    const double t = (rr < 2) ? t1[r] : t2[r];
+    return __builtin_fma(mu, n[r], (rr & 1) ? t : -t);
 }
 WBC_HD inline int32_t qmap_entry(int qp, int mask) { return (int32_t)((qp << 4) | (mask & 15)); }
 constexpr int QMAP_SEG = 4;  // QPs per wave (UPD_RPW of the kernel)
