@@ -24,6 +24,11 @@ RP_LEN = 10
 CN_LEN = 12
 FOOT_NAMES = ("LH", "LF", "RF", "RH")
 
+# the per-robot tables of the default step: name -> row length; the C entry points of table <name> are
+# wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
+TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN}
+TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
+
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
            JBAR=780, BBAR=996, WRENCH=1014, R1=1020, RSW=1032, STAMPS=1044, LEN=1052)
@@ -33,8 +38,7 @@ C_API_SYMBOLS = [
     "wbc_default_params", "wbc_anymal_model", "wbc_create", "wbc_destroy", "wbc_batch", "wbc_set_stream",
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
-    "wbc_last_error", "wbc_model_from_urdf", "wbc_set_robot_params", "wbc_bind_device_robot_params", "wbc_get_robot_params",
-    "wbc_set_contact_normals", "wbc_bind_device_contact_normals", "wbc_get_contact_normals",
+    "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS,
 ]
 
 
@@ -103,17 +107,10 @@ def load_library(path: str = LIB_PATH):
         "wbc_last_kernel_ms": ([P, dp], I32),
         "wbc_last_error": ([], C.c_char_p),
         "wbc_model_from_urdf": ([C.c_char_p, P, P, C.c_char_p, C.POINTER(WbcModel)], I32),
-        "wbc_set_robot_params": ([P, P], I32),
-        "wbc_bind_device_robot_params": ([P, P], I32),
-        "wbc_get_robot_params": ([P, P], I32),
-        "wbc_set_contact_normals": ([P, P], I32),
-        "wbc_bind_device_contact_normals": ([P, P], I32),
-        "wbc_get_contact_normals": ([P, P], I32),
+        **{name: ([P, P], I32) for name in TABLE_SYMBOLS},
     }
     for name, (argt, rest) in sig.items():
-        if name in ("wbc_modes_per_wave", "wbc_set_robot_params", "wbc_bind_device_robot_params",
-                    "wbc_get_robot_params", "wbc_set_contact_normals", "wbc_bind_device_contact_normals",
-                    "wbc_get_contact_normals") and not hasattr(lib, name):
+        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS) and not hasattr(lib, name):
             continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -217,8 +214,7 @@ class Engine:
         self.batch = int(batch)
         self.n_modes = 0
         self._stream = None  # the bound caller stream object (kept alive while bound)
-        self._rp_table = None  # the bound device table's owner (kept alive while bound)
-        self._cn_table = None  # the same for the bound contact-normal table
+        self._bound_tables = {}  # table name -> the bound device table's owner (kept alive while bound)
         self.params = WbcParams.from_buffer_copy(params) if params else default_params()  # the engine-wide wbc_params
         self.h = C.c_void_p()
         rc = self.lib.wbc_create(C.byref(model) if model else None, C.byref(params) if params else None,
@@ -234,8 +230,7 @@ class Engine:
             self.lib.wbc_destroy(self.h)  # synchronizes the bound stream, which is still alive here
             self.h = C.c_void_p()
         self._stream = None
-        self._rp_table = None
-        self._cn_table = None
+        self._bound_tables = {}
 
     def __del__(self):
         try:
@@ -272,49 +267,53 @@ class Engine:
         v = [C.c_void_p(int(p)) if p else None for p in (tau, grf, x, status, iters)]
         self._check(self.lib.wbc_bind_device_outputs(self.h, *v), "wbc_bind_device_outputs")
 
+    # the per-robot tables (TABLES): set from the host, bind a device table, read back
+    def _set_table(self, name, t):
+        self._check(getattr(self.lib, f"wbc_set_{name}")(self.h, _ptr(t)), f"wbc_set_{name}")
+
+    def _bind_table(self, name, table):
+        ptr = int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table or 0)
+        self._check(getattr(self.lib, f"wbc_bind_device_{name}")(self.h, C.c_void_p(ptr) if ptr else None),
+                    f"wbc_bind_device_{name}")
+        self._bound_tables[name] = table if ptr else None
+
+    def _get_table(self, name) -> np.ndarray:
+        out = np.zeros((self.batch, TABLES[name]))
+        self._check(getattr(self.lib, f"wbc_get_{name}")(self.h, _ptr(out)), f"wbc_get_{name}")
+        return out
+
     def set_robot_params(self, table):
         """wbc_set_robot_params: per-robot friction, max_torque, gains and slack_weight for the default
         step.  `table`: an [B, 10] or [B, 9] array (columns ROBOT_PARAM_NAMES), or a dict of column name
         to scalar or length-B array (missing columns: the engine's wbc_params); None clears the table."""
-        t = None if table is None else np.ascontiguousarray(robot_param_table(self.batch, self.params, table))
-        self._check(self.lib.wbc_set_robot_params(self.h, _ptr(t)), "wbc_set_robot_params")
+        self._set_table("robot_params", None if table is None else
+                        np.ascontiguousarray(robot_param_table(self.batch, self.params, table)))
 
     def bind_device_robot_params(self, table=0):
         """wbc_bind_device_robot_params: a caller-owned device table [B, 10] of doubles (no copy, no host
         validation): an integer device pointer, or an object with data_ptr() (a torch tensor), which the
         engine keeps referenced while it is bound.  0 / None: the engine-owned table, or none."""
-        ptr = int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table or 0)
-        self._check(self.lib.wbc_bind_device_robot_params(self.h, C.c_void_p(ptr) if ptr else None),
-                    "wbc_bind_device_robot_params")
-        self._rp_table = table if ptr else None
+        self._bind_table("robot_params", table)
 
     def robot_params(self) -> np.ndarray:
         """wbc_get_robot_params: the [B, 10] table in force (without one: the engine-wide values in B rows)."""
-        out = np.zeros((self.batch, RP_LEN))
-        self._check(self.lib.wbc_get_robot_params(self.h, _ptr(out)), "wbc_get_robot_params")
-        return out
+        return self._get_table("robot_params")
 
     def set_contact_normals(self, normals):
         """wbc_set_contact_normals: the ground normal at each foot of each robot (sloped ground) for the
         default step.  `normals`: a (B, 12) or (B, 4, 3) array, or one (3,) normal / one (4, 3) set
         broadcast to all robots (contact_normal_table); None clears the table: flat ground."""
-        t = None if normals is None else contact_normal_table(self.batch, normals)
-        self._check(self.lib.wbc_set_contact_normals(self.h, _ptr(t)), "wbc_set_contact_normals")
+        self._set_table("contact_normals", None if normals is None else contact_normal_table(self.batch, normals))
 
     def bind_device_contact_normals(self, table=0):
         """wbc_bind_device_contact_normals: a caller-owned device table [B, 12] of doubles (no copy, no
         host validation): an integer device pointer, or an object with data_ptr() (a torch tensor), which
         the engine keeps referenced while it is bound.  0 / None: the engine-owned table, or none."""
-        ptr = int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table or 0)
-        self._check(self.lib.wbc_bind_device_contact_normals(self.h, C.c_void_p(ptr) if ptr else None),
-                    "wbc_bind_device_contact_normals")
-        self._cn_table = table if ptr else None
+        self._bind_table("contact_normals", table)
 
     def contact_normals(self) -> np.ndarray:
         """wbc_get_contact_normals: the [B, 12] table in force (without one: (0, 0, 1) for every foot)."""
-        out = np.zeros((self.batch, CN_LEN))
-        self._check(self.lib.wbc_get_contact_normals(self.h, _ptr(out)), "wbc_get_contact_normals")
-        return out
+        return self._get_table("contact_normals")
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

@@ -23,14 +23,15 @@ extern "C" hipError_t wbc_launch_step(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_stance_step(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve_rp0(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve_cn0(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve_cn1(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_stance_step_cn(const wbc::KernelArgs* a, hipStream_t st);
+// The default step's launchers (wbc_launch_update_solve_<unit> of wbc_kernel_<unit>.hip), indexed by
+// wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's
+#define X(unit) extern "C" hipError_t wbc_launch_update_solve_##unit(const wbc::KernelArgs* a, hipStream_t st);
+WBC_STEP_UNITS(X)
+#undef X
+#define X(unit) wbc_launch_update_solve_##unit,
+static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X)};
+#undef X
+static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_INSTANCES, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
@@ -53,6 +54,26 @@ int32_t fail(int32_t code, const std::string& msg) {
     } while (0)
 }  // namespace
 
+// A per-robot table of the default step ([B][row] doubles): the engine's own device table (allocated
+// at the first set from the host; has_own: it holds a table), a caller's device table, and the one in
+// force: the caller's, else the engine's own when set, else none.
+struct RobotTable {
+    size_t row;
+    double* own = nullptr;
+    bool has_own = false;
+    const double* bound = nullptr;
+    const double* in_force = nullptr;
+    explicit RobotTable(size_t row_len) : row(row_len) {}
+};
+
+// What a step reads and writes: the handle's bindings (wbc_step), or a cycle's packed blocks with
+// the wave map of their masks (enqueue_cycle).  qmap: the map of the engine's own masks.
+struct StepIO {
+    wbc::ConstInputView in;
+    wbc::OutputView out;
+    const int32_t* qmap;
+};
+
 struct wbc_engine {
     int32_t batch = 0;
     int32_t device = 0;
@@ -62,34 +83,23 @@ struct wbc_engine {
     wbc_params* d_params = nullptr;
     double* d_limg = nullptr;  // the step kernel's LDS image of the model + friction table (wbc_layout.h)
     wbc_params params{};  // host copy, passed by value in the kernel arguments (KernelArgs::pv)
-    // per-robot parameters (KernelArgs::rp, [B][WBC_RP_LEN]): the engine's own table (allocated at the
-    // first wbc_set_robot_params; rp_own: it holds a table), a caller's device table, and the one in
-    // force (the caller's, else the engine's own when set, else none: the engine-wide params)
-    double* d_rp = nullptr;
-    bool rp_own = false;
-    const double* rp_bound = nullptr;
-    const double* in_rp = nullptr;
-    // per-robot ground normals at the feet (KernelArgs::cn, [B][WBC_CN_LEN]), held as the parameter
-    // table is: the engine's own table, a caller's device table, the one in force.  The kernels that
-    // read them are per-robot-parameter instances, so without a parameter table in force the step
-    // reads d_rp_uni: the engine-wide params in B rows (built at the first use; params never change)
-    double* d_cn = nullptr;
-    bool cn_own = false;
-    const double* cn_bound = nullptr;
-    const double* in_cn = nullptr;
+    // per-robot parameters (KernelArgs::rp, [B][WBC_RP_LEN]; without a table in force: the
+    // engine-wide params) and per-robot ground normals at the feet (KernelArgs::cn, [B][WBC_CN_LEN];
+    // without: flat ground).  The kernels that read normals are per-robot-parameter instances, so
+    // without a parameter table in force their step reads d_rp_uni: the engine-wide params in B rows
+    // (built at the first use; params never change)
+    RobotTable rp{WBC_RP_LEN};
+    RobotTable cn{WBC_CN_LEN};
     double* d_rp_uni = nullptr;
     // owned inputs: one device block [pose | nu | qj | ref | contacts | switching] (so a host cycle
-    // is one H2D copy), and the outputs one block [tau | grf | status | iters | x]
+    // is one H2D copy), and the outputs one block [tau | grf | status | iters | x] (wbc_layout.h
+    // input_view / output_view: own_in, own_out)
     void* d_inblk = nullptr;
     void* d_outblk = nullptr;
     void* h_in = nullptr;   // pinned staging of the same layouts (wbc_cycle, allocated on first use)
     void* h_out = nullptr;
-    double* d_pose = nullptr;
-    double* d_nu = nullptr;
-    double* d_qj = nullptr;
-    double* d_ref = nullptr;
-    uint8_t* d_contacts = nullptr;
-    uint8_t* d_switching = nullptr;
+    wbc::InputView own_in{};
+    wbc::OutputView own_out{};
     uint8_t* d_mask = nullptr;
     // contact-mode hypotheses (wbc_set_modes): n_modes > 0 turns the inputs into B / n_modes states
     int32_t n_modes = 0;
@@ -99,12 +109,7 @@ struct wbc_engine {
     int32_t mode_loop = 1;
     uint8_t mode_order[16] = {};
     // bound (possibly external) inputs
-    const double* in_pose = nullptr;
-    const double* in_nu = nullptr;
-    const double* in_qj = nullptr;
-    const double* in_ref = nullptr;
-    const uint8_t* in_contacts = nullptr;
-    const uint8_t* in_switching = nullptr;
+    wbc::ConstInputView in{};
     // state / outputs
     double* d_hist = nullptr;
     double* d_work = nullptr;
@@ -117,25 +122,14 @@ struct wbc_engine {
     int32_t modes_stance = 0;
     bool elim = false;        // the last update's choice (its solve follows it)
     int32_t elim_parity = 0;  // and its fallback counter
-    double* d_tau = nullptr;
-    double* d_grf = nullptr;
-    double* d_x = nullptr;
-    int32_t* d_status = nullptr;
-    int32_t* d_iters = nullptr;
     double* d_dbg = nullptr;
     // bound (possibly external) outputs
-    double* out_tau = nullptr;
-    double* out_grf = nullptr;
-    double* out_x = nullptr;
-    int32_t* out_status = nullptr;
-    int32_t* out_iters = nullptr;
+    wbc::OutputView out{};
     // the default step's wave map (KernelArgs::qmap): QPs grouped by contact mask, four to a wave.
     // For the engine's own masks it is built on the host whenever they are copied (qmap_waves waves;
     // 0 = every mask equal, no map needed); for device-bound masks wbc_qmap_kernel builds it on the
     // stream before each step
     int32_t* d_qmap = nullptr;
-    const int32_t* qmap_dev = nullptr;  // the step's map of the engine's own masks: d_qmap, or m_qmap (zero-copy cycle)
-    const uint8_t* m_contacts = nullptr;  // the zero-copy cycle block's masks (device address)
     // a zero-copy cycle ran last: the engine's own input / output blocks (and wave map) are behind the
     // pinned ones until sync_own copies them (before any other call that reads or writes them)
     bool zc_stale = false;
@@ -146,9 +140,10 @@ struct wbc_engine {
     bool timed = false;    // a WBC_TIMED step has recorded ev0 / ev1
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // device addresses of the pinned cycle buffers (zero-copy cycle: the step reads h_in and writes
-    // h_out directly, no copies); null when the batch takes the copy path
-    const void* m_in = nullptr;
-    void* m_out = nullptr;
+    // h_out directly, no copies, and takes the map of its masks from h_qmap); null when the batch
+    // takes the copy path
+    wbc::ConstInputView m_in{};
+    wbc::OutputView m_out{};
     const int32_t* m_qmap = nullptr;
     // the resident control cycle (WBC_RESIDENT): mailbox (pinned, coherent), its stream, whether a
     // resident wave runs and with which step flags, the last command posted, when it last answered
@@ -167,41 +162,35 @@ hipError_t dalloc(T** p, size_t n) {
     return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (n ? n : 1));
 }
 
-// device input / output block sizes (bytes)
-size_t in_block_bytes(size_t B) {
-    return B * (WBC_POSE_LEN + WBC_NU_LEN + WBC_NUM_JOINTS + WBC_REF_LEN) * sizeof(double) + 2 * B;
-}
-size_t out_block_bytes(size_t B) {
-    return B * 2 * WBC_NUM_JOINTS * sizeof(double) + 2 * B * sizeof(int32_t) + B * WBC_NV * sizeof(double);
-}
-
 // wbc_cycle runs zero-copy up to this batch size (enqueue_cycle)
 [[maybe_unused]] constexpr size_t kZeroCopyMaxBatch = 64;
 
 // rows of the input arrays: one per robot, or one per state when mode hypotheses are set
 size_t input_rows(const wbc_engine* h) { return (size_t)(h->n_modes ? h->batch / h->n_modes : h->batch); }
 
-wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) {
+StepIO bound_io(const wbc_engine* h) { return {h->in, h->out, h->d_qmap}; }
+
+wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputView& in, const wbc::OutputView& out) {
     wbc::KernelArgs a;
     a.model = h->d_model;
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    a.rp = h->in_rp ? h->in_rp : (h->in_cn ? h->d_rp_uni : nullptr);
-    a.cn = h->in_cn;
-    a.base_pose = h->in_pose;
-    a.nu = h->in_nu;
-    a.qj = h->in_qj;
-    a.ref = h->in_ref;
-    a.contacts = h->in_contacts;
-    a.switching = h->in_switching;
+    a.rp = h->rp.in_force ? h->rp.in_force : (h->cn.in_force ? h->d_rp_uni : nullptr);
+    a.cn = h->cn.in_force;
+    a.base_pose = in.pose;
+    a.nu = in.nu;
+    a.qj = in.qj;
+    a.ref = in.ref;
+    a.contacts = in.contacts;
+    a.switching = in.switching;
     a.hist = h->d_hist;
     a.work = h->d_work;
-    a.tau = h->out_tau;
-    a.grf = h->out_grf;
-    a.x = (flags & WBC_NO_X) ? nullptr : h->out_x;
-    a.status = h->out_status;
-    a.iters = h->out_iters;
+    a.tau = out.tau;
+    a.grf = out.grf;
+    a.x = (flags & WBC_NO_X) ? nullptr : out.x;
+    a.status = out.status;
+    a.iters = out.iters;
     a.dbg = h->d_dbg;
     a.batch = h->batch;
     a.stateful = (flags & WBC_STATELESS) ? 0 : 1;
@@ -219,6 +208,7 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) {
     std::memset(a.mode_order, 0, sizeof(a.mode_order));
     return a;
 }
+wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) { return make_args(h, flags, h->in, h->out); }
 
 // Host wave map of the engine's own contact masks (copied on the stream; the callers synchronize
 // before the host buffer is reused)
@@ -318,9 +308,9 @@ hipError_t sync_own(wbc_engine* h) {
     if (!h->zc_stale) return hipSuccess;
     const size_t B = (size_t)h->batch;
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_inblk, h->h_in, in_block_bytes(B), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_inblk, h->h_in, wbc::input_block_bytes(B), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(h->d_outblk, h->h_out, out_block_bytes(B), hipMemcpyHostToDevice, h->stream);
+        e = hipMemcpyAsync(h->d_outblk, h->h_out, wbc::output_block_bytes(B), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && h->qmap_waves)
         e = hipMemcpyAsync(h->d_qmap, h->h_qmap, (size_t)h->qmap_waves * wbc::QMAP_SEG * sizeof(int32_t),
                            hipMemcpyHostToDevice, h->stream);
@@ -335,7 +325,7 @@ hipError_t sync_own(wbc_engine* h) {
 void begin_update(wbc_engine* h, wbc::KernelArgs& a) {
     bool all = false;
     if (h->n_modes) all = h->modes_stance == h->n_modes;
-    else if (h->in_contacts == h->d_contacts) all = h->n_stance_own == h->batch;
+    else if (a.contacts == h->own_in.contacts) all = h->n_stance_own == h->batch;
     h->elim = all;
     // the fallback counters alternate between elimination updates only: the update with parity p
     // fills fb[p] and clears fb[p ^ 1], which only the next elimination update uses (an update
@@ -346,13 +336,19 @@ void begin_update(wbc_engine* h, wbc::KernelArgs& a) {
     a.parity = h->elim_parity;
 }
 
+// The step reads the engine's own masks (copied by the host, counted and mapped at copy time): those
+// of its own input block, or of the zero-copy cycle's pinned block
+bool own_masks(const wbc_engine* h, const wbc::KernelArgs& a) {
+    return a.contacts == h->own_in.contacts || (h->m_in.contacts && a.contacts == h->m_in.contacts);
+}
+
 // The default step (wbc_update_solve_kernel: every QP reduced to 12 variables and solved in the
 // update wave) solves its own fallbacks in the wave that found them (no list), so it
 // leaves the fallback list and its parity to the split path's elimination updates.  Its waves each
-// hold QPs of one contact mask: the wave map (the engine's own masks: built when they were copied;
-// device-bound masks: built on the stream now under WBC_GROUP), or under mode hypotheses the
-// arithmetic map.
-hipError_t begin_step16(wbc_engine* h, wbc::KernelArgs& a, uint32_t flags) {
+// hold QPs of one contact mask: the wave map (the engine's own masks: built when they were copied,
+// `qmap` its device address; device-bound masks: built on the stream now under WBC_GROUP), or under
+// mode hypotheses the arithmetic map.
+hipError_t begin_step16(wbc_engine* h, wbc::KernelArgs& a, uint32_t flags, const int32_t* qmap) {
     a.elim = 1;
     h->elim = false;  // a later wbc_solve needs its own wbc_update
     if (a.modes) {
@@ -360,10 +356,10 @@ hipError_t begin_step16(wbc_engine* h, wbc::KernelArgs& a, uint32_t flags) {
         a.nwaves = ((S + wbc::QMAP_SEG - 1) / wbc::QMAP_SEG) * a.modes;
         return hipSuccess;
     }
-    if ((h->in_contacts == h->d_contacts || (h->m_contacts && h->in_contacts == h->m_contacts)) && h->qmap_host) {
+    if (own_masks(h, a) && h->qmap_host) {
 #ifndef WBC_NO_QMAP  // (A/B builds only: the unmapped step)
         if (h->qmap_waves) {
-            a.qmap = h->qmap_dev;
+            a.qmap = qmap;
             a.nwaves = h->qmap_waves;
         }
 #endif
@@ -374,7 +370,7 @@ hipError_t begin_step16(wbc_engine* h, wbc::KernelArgs& a, uint32_t flags) {
     if (!(flags & WBC_GROUP)) return hipSuccess;
     a.qmap = h->d_qmap;
     a.nwaves = wbc::qmap_capacity(h->batch) / wbc::QMAP_SEG;
-    return wbc_launch_qmap(h->in_contacts, h->batch, h->d_qmap, h->stream);
+    return wbc_launch_qmap(a.contacts, h->batch, h->d_qmap, h->stream);
 }
 
 // The default step's QPs are all stance QPs of the stance form: stateless, the engine's own masks
@@ -383,8 +379,7 @@ bool step_all_stance(const wbc_engine* h, const wbc::KernelArgs& a) {
 #ifdef WBC_NO_STANCE_TU  // (A/B builds only: the mixed-form kernel for every step)
     return false;
 #else
-    const bool own = h->in_contacts == h->d_contacts || (h->m_contacts && h->in_contacts == h->m_contacts);
-    return own && h->qmap_host && h->n_stance_own == h->batch && !a.stateful && !a.modes && !a.qmap;
+    return own_masks(h, a) && h->qmap_host && h->n_stance_own == h->batch && !a.stateful && !a.modes && !a.qmap;
 #endif
 }
 
@@ -392,6 +387,23 @@ hipError_t launch_solves(wbc_engine* h, wbc::KernelArgs& a) {
     a.elim = h->elim ? 1 : 0;
     a.parity = h->elim_parity;
     return h->elim ? wbc_launch_solve_stance(&a, h->stream) : wbc_launch_solve_general(&a, h->stream);
+}
+
+// The per-robot tables are read by the default wbc_step (and the plain wbc_cycle) only: with one in
+// force `call` is refused, outright (forms = 0) or when `flags` ask for one of `forms`.  The
+// parameter table is named before the normals; `allowed` says what the call may still do.
+int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uint32_t forms, const char* allowed) {
+    if (forms && !(flags & forms)) return WBC_OK;
+    const char* form = !forms ? nullptr : (flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT";
+    for (const bool cn : {false, true}) {
+        if (!(cn ? h->cn : h->rp).in_force) continue;
+        const std::string what = cn ? "contact normals" : "a per-robot parameter table";
+        return fail(WBC_ERR_STATE, std::string(call) + ": " +
+                                       (form ? form + (" with " + what) + " in force" : what + (cn ? " are in force" : " is in force")) +
+                                       " (" + allowed + "; clear " + (cn ? "them with wbc_set_contact_normals" : "it with wbc_set_robot_params") +
+                                       "(h, NULL))");
+    }
+    return WBC_OK;
 }
 }  // namespace
 
@@ -454,26 +466,13 @@ int32_t wbc_create(const wbc_model* model, const wbc_params* params, int32_t bat
     ALLOC(d_params, 1);
     ALLOC(d_limg, wbc::LIMG_LEN);
     // (the input block in whole 8-byte words: the resident cycle copies it by words)
-    if (hipMalloc(&h->d_inblk, (in_block_bytes(B) + 7) / 8 * 8) != hipSuccess ||
-        hipMalloc(&h->d_outblk, out_block_bytes(B)) != hipSuccess) {
+    if (hipMalloc(&h->d_inblk, 8 * wbc::input_block_words(B)) != hipSuccess ||
+        hipMalloc(&h->d_outblk, wbc::output_block_bytes(B)) != hipSuccess) {
         wbc_destroy(h);
         return fail(WBC_ERR_HIP, "hipMalloc failed: input/output blocks");
     }
-    {
-        double* in = static_cast<double*>(h->d_inblk);
-        h->d_pose = in;
-        h->d_nu = h->d_pose + B * WBC_POSE_LEN;
-        h->d_qj = h->d_nu + B * WBC_NU_LEN;
-        h->d_ref = h->d_qj + B * WBC_NUM_JOINTS;
-        h->d_contacts = reinterpret_cast<uint8_t*>(h->d_ref + B * WBC_REF_LEN);
-        h->d_switching = h->d_contacts + B;
-        double* out = static_cast<double*>(h->d_outblk);
-        h->d_tau = out;
-        h->d_grf = h->d_tau + B * WBC_NUM_JOINTS;
-        h->d_status = reinterpret_cast<int32_t*>(h->d_grf + B * WBC_NUM_JOINTS);
-        h->d_iters = h->d_status + B;
-        h->d_x = reinterpret_cast<double*>(h->d_iters + B);  // status + iters = 8 B per robot: aligned
-    }
+    h->own_in = wbc::input_view(h->d_inblk, B);
+    h->own_out = wbc::output_view(h->d_outblk, B);
     ALLOC(d_mask, B);
     ALLOC(d_modes, WBC_MAX_MODES);
     ALLOC(d_hist, B * wbc::HIST_LEN);
@@ -486,7 +485,6 @@ int32_t wbc_create(const wbc_model* model, const wbc_params* params, int32_t bat
         wbc_destroy(h);
         return fail(WBC_ERR_HIP, "hipHostMalloc failed: wave map");
     }
-    h->qmap_dev = h->d_qmap;
     if (B <= (size_t)wbc::QMAP_SEG) {  // the resident cycle's code and mailbox, made ready now
         (void)wbc_preload_resident();
         if (resident_alloc(h) != hipSuccess) {
@@ -501,34 +499,25 @@ int32_t wbc_create(const wbc_model* model, const wbc_params* params, int32_t bat
     }
     h->stream = h->own_stream;
     h->n_stance_own = B;  // d_contacts starts as all-stance (15), below
-    h->in_pose = h->d_pose;
-    h->in_nu = h->d_nu;
-    h->in_qj = h->d_qj;
-    h->in_ref = h->d_ref;
-    h->in_contacts = h->d_contacts;
-    h->in_switching = h->d_switching;
-    h->out_tau = h->d_tau;
-    h->out_grf = h->d_grf;
-    h->out_x = h->d_x;
-    h->out_status = h->d_status;
-    h->out_iters = h->d_iters;
+    h->in = wbc::const_view(h->own_in);
+    h->out = h->own_out;
     hipStream_t st = h->stream;
     wbc::LdsImage limg;
     wbc::build_lds_image(m, p.friction, limg);
     if (hipMemcpyAsync(h->d_model, &m, sizeof(m), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(h->d_params, &p, sizeof(p), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(h->d_limg, &limg, sizeof(limg), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(h->d_pose, 0, B * WBC_POSE_LEN * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_nu, 0, B * WBC_NU_LEN * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_qj, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_ref, 0, B * WBC_REF_LEN * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_contacts, 15, B, st) != hipSuccess ||
-        hipMemsetAsync(h->d_switching, 0, B, st) != hipSuccess ||
-        hipMemsetAsync(h->d_status, 0, B * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(h->d_iters, 0, B * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(h->d_tau, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_grf, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
-        hipMemsetAsync(h->d_x, 0, B * WBC_NV * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.pose, 0, B * WBC_POSE_LEN * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.nu, 0, B * WBC_NU_LEN * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.qj, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.ref, 0, B * WBC_REF_LEN * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.contacts, 15, B, st) != hipSuccess ||
+        hipMemsetAsync(h->own_in.switching, 0, B, st) != hipSuccess ||
+        hipMemsetAsync(h->own_out.status, 0, B * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(h->own_out.iters, 0, B * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(h->own_out.tau, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_out.grf, 0, B * WBC_NUM_JOINTS * sizeof(double), st) != hipSuccess ||
+        hipMemsetAsync(h->own_out.x, 0, B * WBC_NV * sizeof(double), st) != hipSuccess ||
         hipMemsetAsync(h->d_dbg, 0, B * WBC_DBG_LEN * sizeof(double), st) != hipSuccess ||
         hipMemsetAsync(h->d_fb, 0, (2 + B) * sizeof(int32_t), st) != hipSuccess ||
         wbc_launch_reset(h->d_hist, nullptr, batch, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
@@ -553,7 +542,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_box) (void)hipHostFree(h->res_box);
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
-                    h->d_fb, h->d_dbg, h->d_qmap, h->d_rp, h->d_cn, h->d_rp_uni};
+                    h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -586,9 +575,9 @@ int32_t wbc_set_state(wbc_engine* h, const double* base_pose, const double* nu, 
     WBC_HIP(sync_own(h));
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = input_rows(h);
-    if (base_pose) { WBC_HIP(hipMemcpyAsync(h->d_pose, base_pose, B * WBC_POSE_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in_pose = h->d_pose; }
-    if (nu) { WBC_HIP(hipMemcpyAsync(h->d_nu, nu, B * WBC_NU_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in_nu = h->d_nu; }
-    if (qj) { WBC_HIP(hipMemcpyAsync(h->d_qj, qj, B * WBC_NUM_JOINTS * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in_qj = h->d_qj; }
+    if (base_pose) { WBC_HIP(hipMemcpyAsync(h->own_in.pose, base_pose, B * WBC_POSE_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in.pose = h->own_in.pose; }
+    if (nu) { WBC_HIP(hipMemcpyAsync(h->own_in.nu, nu, B * WBC_NU_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in.nu = h->own_in.nu; }
+    if (qj) { WBC_HIP(hipMemcpyAsync(h->own_in.qj, qj, B * WBC_NUM_JOINTS * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in.qj = h->own_in.qj; }
     WBC_HIP(hipStreamSynchronize(h->stream));  // host buffers may be reused by the caller
     return WBC_OK;
 }
@@ -598,15 +587,15 @@ int32_t wbc_set_reference(wbc_engine* h, const double* ref, const uint8_t* conta
     WBC_HIP(sync_own(h));
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = input_rows(h);
-    if (ref) { WBC_HIP(hipMemcpyAsync(h->d_ref, ref, B * WBC_REF_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in_ref = h->d_ref; }
+    if (ref) { WBC_HIP(hipMemcpyAsync(h->own_in.ref, ref, B * WBC_REF_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream)); h->in.ref = h->own_in.ref; }
     if (contacts) {
-        WBC_HIP(hipMemcpyAsync(h->d_contacts, contacts, B, hipMemcpyHostToDevice, h->stream));
-        h->in_contacts = h->d_contacts;
+        WBC_HIP(hipMemcpyAsync(h->own_in.contacts, contacts, B, hipMemcpyHostToDevice, h->stream));
+        h->in.contacts = h->own_in.contacts;
         h->n_stance_own = count_stance(contacts, B);
         // the wave map of these masks (rows = QPs; under mode hypotheses contacts[] is not read)
         if (!h->n_modes) WBC_HIP(upload_qmap(h, contacts));
     }
-    if (switching) { WBC_HIP(hipMemcpyAsync(h->d_switching, switching, B, hipMemcpyHostToDevice, h->stream)); h->in_switching = h->d_switching; }
+    if (switching) { WBC_HIP(hipMemcpyAsync(h->own_in.switching, switching, B, hipMemcpyHostToDevice, h->stream)); h->in.switching = h->own_in.switching; }
     WBC_HIP(hipStreamSynchronize(h->stream));
     return WBC_OK;
 }
@@ -614,88 +603,37 @@ int32_t wbc_set_reference(wbc_engine* h, const double* ref, const uint8_t* conta
 int32_t wbc_bind_device_inputs(wbc_engine* h, const double* d_base_pose, const double* d_nu, const double* d_qj,
                                const double* d_ref, const uint8_t* d_contacts, const uint8_t* d_switching) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
-    h->in_pose = d_base_pose ? d_base_pose : h->d_pose;
-    h->in_nu = d_nu ? d_nu : h->d_nu;
-    h->in_qj = d_qj ? d_qj : h->d_qj;
-    h->in_ref = d_ref ? d_ref : h->d_ref;
-    h->in_contacts = d_contacts ? d_contacts : h->d_contacts;
-    h->in_switching = d_switching ? d_switching : h->d_switching;
+    h->in.pose = d_base_pose ? d_base_pose : h->own_in.pose;
+    h->in.nu = d_nu ? d_nu : h->own_in.nu;
+    h->in.qj = d_qj ? d_qj : h->own_in.qj;
+    h->in.ref = d_ref ? d_ref : h->own_in.ref;
+    h->in.contacts = d_contacts ? d_contacts : h->own_in.contacts;
+    h->in.switching = d_switching ? d_switching : h->own_in.switching;
     return WBC_OK;
 }
 
 int32_t wbc_bind_device_outputs(wbc_engine* h, double* d_tau, double* d_grf, double* d_x, int32_t* d_status,
                                 int32_t* d_iters) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
-    h->out_tau = d_tau ? d_tau : h->d_tau;
-    h->out_grf = d_grf ? d_grf : h->d_grf;
-    h->out_x = d_x ? d_x : h->d_x;
-    h->out_status = d_status ? d_status : h->d_status;
-    h->out_iters = d_iters ? d_iters : h->d_iters;
+    h->out.tau = d_tau ? d_tau : h->own_out.tau;
+    h->out.grf = d_grf ? d_grf : h->own_out.grf;
+    h->out.x = d_x ? d_x : h->own_out.x;
+    h->out.status = d_status ? d_status : h->own_out.status;
+    h->out.iters = d_iters ? d_iters : h->own_out.iters;
     return WBC_OK;
 }
 
-int32_t wbc_set_robot_params(wbc_engine* h, const double* table) {
-    if (!h) return fail(WBC_ERR_ARG, "null handle");
-    if (!table) {  // back to the engine-wide params (or to a caller's bound table)
-        h->rp_own = false;
-        h->in_rp = h->rp_bound;
-        return WBC_OK;
-    }
-    static const char* const names[WBC_RP_LEN - 1] = {"friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing",
-                                                      "slack_weight"};
-    const size_t B = (size_t)h->batch;
-    for (size_t b = 0; b < B; ++b) {
-        const int c = wbc::rp_bad_column(table + b * WBC_RP_LEN);
-        if (c >= 0) {
-            char val[32];
-            std::snprintf(val, sizeof(val), "%g", table[b * WBC_RP_LEN + c]);
-            return fail(WBC_ERR_ARG, "wbc_set_robot_params: row " + std::to_string(b) + ", column " + std::to_string(c) + " (" +
-                                         names[c] + ") = " + val +
-                                         ": need finite entries, friction >= 0, max_torque >= 0, slack_weight > 0");
-        }
-    }
-    WBC_HIP(sync_own(h));
-    WBC_HIP(hipSetDevice(h->device));
-    if (!h->d_rp && dalloc(&h->d_rp, B * WBC_RP_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_rp");
-    WBC_HIP(hipMemcpyAsync(h->d_rp, table, B * WBC_RP_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    WBC_HIP(hipStreamSynchronize(h->stream));  // the host table may be reused by the caller
-    h->rp_own = true;
-    if (!h->rp_bound) h->in_rp = h->d_rp;
-    return WBC_OK;
+// the engine-wide params as a row of the parameter table (the reserved column 0)
+static void rp_engine_row(const wbc_params& p, double* row) {
+    const double r[WBC_RP_LEN] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight, 0.0};
+    std::memcpy(row, r, sizeof(r));
 }
-
-int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table) {
-    if (!h) return fail(WBC_ERR_ARG, "null handle");
-    if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
-        return fail(WBC_ERR_ARG, "wbc_bind_device_robot_params: the table must be 16-byte aligned");
-    h->rp_bound = d_table;
-    h->in_rp = d_table ? d_table : (h->rp_own ? h->d_rp : nullptr);
-    return WBC_OK;
-}
-
-int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
-    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
-    const size_t B = (size_t)h->batch;
-    if (h->in_rp) {
-        WBC_HIP(sync_own(h));
-        WBC_HIP(hipSetDevice(h->device));
-        WBC_HIP(hipMemcpyAsync(table, h->in_rp, B * WBC_RP_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        WBC_HIP(hipStreamSynchronize(h->stream));
-    } else {
-        const wbc_params& p = h->params;
-        const double row[WBC_RP_LEN - 1] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight};
-        for (size_t b = 0; b < B; ++b) std::memcpy(table + b * WBC_RP_LEN, row, sizeof(row));
-    }
-    for (size_t b = 0; b < B; ++b) table[b * WBC_RP_LEN + WBC_RP_LEN - 1] = 0.0;
-    return WBC_OK;
-}
-
 // the uniform parameter table the contact-normal kernels read when no parameter table is in force
 static int32_t ensure_rp_uniform(wbc_engine* h) {
     if (h->d_rp_uni) return WBC_OK;
     const size_t B = (size_t)h->batch;
-    const wbc_params& p = h->params;
-    const double row[WBC_RP_LEN] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight, 0.0};
+    double row[WBC_RP_LEN];
+    rp_engine_row(h->params, row);
     std::vector<double> t(B * WBC_RP_LEN);
     for (size_t b = 0; b < B; ++b) std::memcpy(t.data() + b * WBC_RP_LEN, row, sizeof(row));
     WBC_HIP(hipSetDevice(h->device));
@@ -710,61 +648,113 @@ static int32_t ensure_rp_uniform(wbc_engine* h) {
     return WBC_OK;
 }
 
-int32_t wbc_set_contact_normals(wbc_engine* h, const double* table) {
+// The three calls of a per-robot table (RobotTable), for the parameters and for the normals.  What
+// differs is passed in: `call` (the C entry point, for messages), `what` (the own table's name in
+// allocation errors), row_error (why the host refuses row b, or "" for a row it accepts), uniform_rp
+// (the table's kernels read a parameter table too: ensure_rp_uniform) and, to read back without a
+// table in force, the default rows.
+// Set from the host: a refused table leaves the previous one in force.
+static int32_t table_set(wbc_engine* h, RobotTable wbc_engine::*which, const double* table, const char* call,
+                         const char* what, std::string (*row_error)(const double* row), bool uniform_rp) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
-    if (!table) {  // back to flat ground (or to a caller's bound table)
-        h->cn_own = false;
-        h->in_cn = h->cn_bound;
+    RobotTable& t = h->*which;
+    if (!table) {  // back to no table of the engine's own (or to a caller's bound table)
+        t.has_own = false;
+        t.in_force = t.bound;
         return WBC_OK;
     }
-    static const char* const feet[WBC_NUM_LEGS] = {"LH", "LF", "RF", "RH"};
     const size_t B = (size_t)h->batch;
     for (size_t b = 0; b < B; ++b) {
-        const int l = wbc::cn_bad_foot(table + b * WBC_CN_LEN);
-        if (l >= 0) {
-            const double* m = table + b * WBC_CN_LEN + 3 * l;
-            char val[96];
-            std::snprintf(val, sizeof(val), "(%g, %g, %g)", m[0], m[1], m[2]);
-            return fail(WBC_ERR_ARG, "wbc_set_contact_normals: row " + std::to_string(b) + ", foot " + std::to_string(l) + " (" +
-                                         feet[l] + ") = " + val +
-                                         ": need finite entries, 0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5");
-        }
+        const std::string why = row_error(table + b * t.row);
+        if (!why.empty()) return fail(WBC_ERR_ARG, std::string(call) + ": row " + std::to_string(b) + ", " + why);
     }
     WBC_HIP(sync_own(h));
-    if (const int32_t rc = ensure_rp_uniform(h)) return rc;
-    WBC_HIP(hipSetDevice(h->device));
-    if (!h->d_cn && dalloc(&h->d_cn, B * WBC_CN_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_cn");
-    WBC_HIP(hipMemcpyAsync(h->d_cn, table, B * WBC_CN_LEN * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    WBC_HIP(hipStreamSynchronize(h->stream));  // the host table may be reused by the caller
-    h->cn_own = true;
-    if (!h->cn_bound) h->in_cn = h->d_cn;
-    return WBC_OK;
-}
-
-int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table) {
-    if (!h) return fail(WBC_ERR_ARG, "null handle");
-    if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
-        return fail(WBC_ERR_ARG, "wbc_bind_device_contact_normals: the table must be 16-byte aligned");
-    if (d_table) {
+    if (uniform_rp) {
         if (const int32_t rc = ensure_rp_uniform(h)) return rc;
     }
-    h->cn_bound = d_table;
-    h->in_cn = d_table ? d_table : (h->cn_own ? h->d_cn : nullptr);
+    WBC_HIP(hipSetDevice(h->device));
+    if (!t.own && dalloc(&t.own, B * t.row) != hipSuccess) return fail(WBC_ERR_HIP, std::string("hipMalloc failed: ") + what);
+    WBC_HIP(hipMemcpyAsync(t.own, table, B * t.row * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));  // the host table may be reused by the caller
+    t.has_own = true;
+    if (!t.bound) t.in_force = t.own;
+    return WBC_OK;
+}
+// Bind a caller's device table (no copy, no host validation), or unbind it (null)
+static int32_t table_bind(wbc_engine* h, RobotTable wbc_engine::*which, const double* d_table, const char* call,
+                          bool uniform_rp) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    RobotTable& t = h->*which;
+    if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
+        return fail(WBC_ERR_ARG, std::string(call) + ": the table must be 16-byte aligned");
+    if (d_table && uniform_rp) {
+        if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    }
+    t.bound = d_table;
+    t.in_force = d_table ? d_table : (t.has_own ? t.own : nullptr);
+    return WBC_OK;
+}
+// Read back the table in force, or `defaults` in every row
+static int32_t table_get(wbc_engine* h, RobotTable wbc_engine::*which, double* table, const double* defaults) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    const RobotTable& t = h->*which;
+    const size_t B = (size_t)h->batch;
+    if (t.in_force) {
+        WBC_HIP(sync_own(h));
+        WBC_HIP(hipSetDevice(h->device));
+        WBC_HIP(hipMemcpyAsync(table, t.in_force, B * t.row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        WBC_HIP(hipStreamSynchronize(h->stream));
+    } else {
+        for (size_t b = 0; b < B; ++b) std::memcpy(table + b * t.row, defaults, t.row * sizeof(double));
+    }
     return WBC_OK;
 }
 
-int32_t wbc_get_contact_normals(wbc_engine* h, double* table) {
+static std::string rp_row_error(const double* row) {
+    static const char* const names[WBC_RP_LEN - 1] = {"friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing",
+                                                      "slack_weight"};
+    const int c = wbc::rp_bad_column(row);
+    if (c < 0) return "";
+    char val[32];
+    std::snprintf(val, sizeof(val), "%g", row[c]);
+    return "column " + std::to_string(c) + " (" + names[c] + ") = " + val +
+           ": need finite entries, friction >= 0, max_torque >= 0, slack_weight > 0";
+}
+static std::string cn_row_error(const double* row) {
+    static const char* const feet[WBC_NUM_LEGS] = {"LH", "LF", "RF", "RH"};
+    const int l = wbc::cn_bad_foot(row);
+    if (l < 0) return "";
+    const double* m = row + 3 * l;
+    char val[96];
+    std::snprintf(val, sizeof(val), "(%g, %g, %g)", m[0], m[1], m[2]);
+    return "foot " + std::to_string(l) + " (" + feet[l] + ") = " + val +
+           ": need finite entries, 0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5";
+}
+
+int32_t wbc_set_robot_params(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::rp, table, "wbc_set_robot_params", "d_rp", rp_row_error, false);
+}
+int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::rp, d_table, "wbc_bind_device_robot_params", false);
+}
+int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
     if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
-    const size_t B = (size_t)h->batch;
-    if (h->in_cn) {
-        WBC_HIP(sync_own(h));
-        WBC_HIP(hipSetDevice(h->device));
-        WBC_HIP(hipMemcpyAsync(table, h->in_cn, B * WBC_CN_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        WBC_HIP(hipStreamSynchronize(h->stream));
-    } else {
-        for (size_t e = 0; e < B * WBC_CN_LEN; ++e) table[e] = (e % 3 == 2) ? 1.0 : 0.0;
-    }
+    double row[WBC_RP_LEN];
+    rp_engine_row(h->params, row);
+    if (const int32_t rc = table_get(h, &wbc_engine::rp, table, row)) return rc;
+    for (size_t b = 0; b < (size_t)h->batch; ++b) table[b * WBC_RP_LEN + WBC_RP_LEN - 1] = 0.0;  // the reserved column
     return WBC_OK;
+}
+
+int32_t wbc_set_contact_normals(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::cn, table, "wbc_set_contact_normals", "d_cn", cn_row_error, true);
+}
+int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::cn, d_table, "wbc_bind_device_contact_normals", true);
+}
+int32_t wbc_get_contact_normals(wbc_engine* h, double* table) {
+    static const double flat[WBC_CN_LEN] = {0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0};
+    return table_get(h, &wbc_engine::cn, table, flat);
 }
 
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
@@ -786,8 +776,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
-    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_update: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
-    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_update: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
+    if (const int32_t rc = refuse_tables(h, "wbc_update", flags, 0, "default wbc_step only")) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -800,8 +789,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_solve: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
-    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_solve: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
-    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_solve: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
+    if (const int32_t rc = refuse_tables(h, "wbc_solve", flags, 0, "default wbc_step only")) return rc;
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
@@ -809,20 +797,14 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     return WBC_OK;  // the assembled problem stays valid: solving it again gives the same result
 }
 
-int32_t wbc_step(wbc_engine* h, uint32_t flags) {
-    if (!h) return fail(WBC_ERR_ARG, "null handle");
+// One step on the inputs, outputs and wave map of `io` (wbc_step: the handle's bindings;
+// enqueue_cycle: the cycle's blocks)
+static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
-    if (h->in_rp && (flags & (WBC_SPLIT | WBC_FUSED)))
-        return fail(WBC_ERR_STATE, std::string("wbc_step: ") + ((flags & WBC_SPLIT) ? "WBC_SPLIT" : "WBC_FUSED") +
-                                       " with a per-robot parameter table in force (default form only; clear it with "
-                                       "wbc_set_robot_params(h, NULL))");
-    if (h->in_cn && (flags & (WBC_SPLIT | WBC_FUSED)))
-        return fail(WBC_ERR_STATE, std::string("wbc_step: ") + ((flags & WBC_SPLIT) ? "WBC_SPLIT" : "WBC_FUSED") +
-                                       " with contact normals in force (default form only; clear them with "
-                                       "wbc_set_contact_normals(h, NULL))");
+    if (const int32_t rc = refuse_tables(h, "wbc_step", flags, WBC_SPLIT | WBC_FUSED, "default form only")) return rc;
     WBC_HIP(hipSetDevice(h->device));
-    wbc::KernelArgs a = make_args(h, flags);
+    wbc::KernelArgs a = make_args(h, flags, io.in, io.out);
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
     if (timed) WBC_HIP(hipEventRecord(h->ev0, h->stream));
     if (flags & WBC_SPLIT) {
@@ -833,21 +815,14 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
     } else if (flags & WBC_FUSED) {
         WBC_HIP(wbc_launch_step(&a, h->stream));  // one robot per wave, the general method
     } else {
-        // default: one kernel, every QP reduced to 12 variables and solved in the update wave; a
-        // stateless step whose masks the host knows to be all 15 (no map then) runs the stance-only
-        // instance, scheduled for it alone (wbc_kernel_stance.hip)
-        // a per-robot parameter table in force: the same three choices among its own instances
-        // (wbc_kernel_rps.hip stance-only, wbc_kernel_rp0.hip stateless, wbc_kernel_rp1.hip stateful)
-        WBC_HIP(begin_step16(h, a, flags));
-        // contact normals in force: their instances (wbc_kernel_cns.hip, wbc_kernel_cn0.hip,
-        // wbc_kernel_cn1.hip), which read the parameter table too (the caller's, or the
-        // engine's uniform one)
-        if (a.cn && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_cn(&a, h->stream));
-        else if (a.cn) WBC_HIP(a.stateful ? wbc_launch_update_solve_cn1(&a, h->stream) : wbc_launch_update_solve_cn0(&a, h->stream));
-        else if (a.rp && step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step_rp(&a, h->stream));
-        else if (a.rp) WBC_HIP(a.stateful ? wbc_launch_update_solve_rp1(&a, h->stream) : wbc_launch_update_solve_rp0(&a, h->stream));
-        else if (step_all_stance(h, a)) WBC_HIP(wbc_launch_stance_step(&a, h->stream));
-        else WBC_HIP(wbc_launch_update_solve(&a, h->stream));
+        // default: one kernel, every QP reduced to 12 variables and solved in the update wave.  Its
+        // instance (wbc_layout.h step_instance, one kernel unit each): a stateless step whose masks the
+        // host knows to be all 15 (no map then) runs the stance-only one, scheduled for it alone
+        // (DESIGN.md 4.22), any other step the stateless or the stateful one; the same three under a
+        // per-robot parameter table in force and under contact normals, which read the
+        // parameter table too (the caller's, or the engine's uniform one)
+        WBC_HIP(begin_step16(h, a, flags, io.qmap));
+        WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0)](&a, h->stream));
     }
     if (timed) {
         WBC_HIP(hipEventRecord(h->ev1, h->stream));
@@ -855,6 +830,11 @@ int32_t wbc_step(wbc_engine* h, uint32_t flags) {
     }
     h->updated = false;
     return WBC_OK;
+}
+
+int32_t wbc_step(wbc_engine* h, uint32_t flags) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    return step_on(h, flags, bound_io(h));
 }
 
 int32_t wbc_set_modes(wbc_engine* h, int32_t n_modes, const uint8_t* modes) {
@@ -884,8 +864,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
     if (!h->n_modes) return fail(WBC_ERR_STATE, "wbc_step_modes: no mode hypotheses set (wbc_set_modes)");
-    if (h->in_rp) return fail(WBC_ERR_STATE, "wbc_step_modes: a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))");
-    if (h->in_cn) return fail(WBC_ERR_STATE, "wbc_step_modes: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))");
+    if (const int32_t rc = refuse_tables(h, "wbc_step_modes", flags, 0, "default wbc_step only")) return rc;
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
     WBC_HIP(hipSetDevice(h->device));
@@ -912,8 +891,8 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
         WBC_HIP(wbc_launch_modes(&a, h->stream));
     } else {
         // default: each hypothesis reduced and solved in its own 16-lane segment
-        WBC_HIP(begin_step16(h, a, flags));
-        WBC_HIP(wbc_launch_update_solve(&a, h->stream));
+        WBC_HIP(begin_step16(h, a, flags, h->d_qmap));
+        WBC_HIP(kStepLaunchers[wbc::step_instance(false, false, false, a.stateful != 0)](&a, h->stream));
     }
     if (timed) {
         WBC_HIP(hipEventRecord(h->ev1, h->stream));
@@ -927,51 +906,29 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
 namespace {
 // One cycle's device work on the engine stream, from the packed pinned inputs (h_in) to the packed
 // pinned outputs (h_out): one H2D copy, the wave map's copy when the masks differ, the step on the
-// engine's own input and output buffers (caller bindings are restored afterwards), one D2H copy
-// (x, last in the block, only without WBC_NO_X).
+// engine's own input and output blocks (the caller's bindings stay as they are), one D2H copy (x,
+// last in the block, only without WBC_NO_X).
 int32_t enqueue_cycle(wbc_engine* h, uint32_t flags) {
     h->zc_stale = false;  // this cycle's blocks replace whatever was pending
     const size_t B = (size_t)h->batch;
-    const size_t inb = in_block_bytes(B), outb = out_block_bytes(B), xb = B * WBC_NV * sizeof(double);
-    const bool zc = h->m_in != nullptr;
+    const bool zc = h->m_in.pose != nullptr;
     if (!zc) {
-        WBC_HIP(hipMemcpyAsync(h->d_inblk, h->h_in, inb, hipMemcpyHostToDevice, h->stream));
+        WBC_HIP(hipMemcpyAsync(h->d_inblk, h->h_in, wbc::input_block_bytes(B), hipMemcpyHostToDevice, h->stream));
         if (h->qmap_waves)
             WBC_HIP(hipMemcpyAsync(h->d_qmap, h->h_qmap, (size_t)h->qmap_waves * wbc::QMAP_SEG * sizeof(int32_t),
                                    hipMemcpyHostToDevice, h->stream));
     }
     // the step's input and output block: the engine's device buffers, or (zero-copy) the pinned
     // host buffers through their device addresses, in the same layouts
-    const double* ib = zc ? static_cast<const double*>(h->m_in) : static_cast<const double*>(h->d_inblk);
-    double* ob = zc ? static_cast<double*>(h->m_out) : static_cast<double*>(h->d_outblk);
-    const double* const ip = h->in_pose; const double* const in = h->in_nu; const double* const iq = h->in_qj;
-    const double* const ir = h->in_ref; const uint8_t* const ic = h->in_contacts; const uint8_t* const is = h->in_switching;
-    h->in_pose = ib;
-    h->in_nu = ib + B * WBC_POSE_LEN;
-    h->in_qj = h->in_nu + B * WBC_NU_LEN;
-    h->in_ref = h->in_qj + B * WBC_NUM_JOINTS;
-    h->in_contacts = reinterpret_cast<const uint8_t*>(h->in_ref + B * WBC_REF_LEN);
-    h->in_switching = h->in_contacts + B;
-    double* const bt = h->out_tau; double* const bg = h->out_grf; double* const bx = h->out_x;
-    int32_t* const bs = h->out_status; int32_t* const bi = h->out_iters;
-    h->out_tau = ob;
-    h->out_grf = ob + B * WBC_NUM_JOINTS;
-    h->out_status = reinterpret_cast<int32_t*>(h->out_grf + B * WBC_NUM_JOINTS);
-    h->out_iters = h->out_status + B;
-    h->out_x = reinterpret_cast<double*>(h->out_iters + B);
-    const int32_t* const qm = h->qmap_dev;
-    if (zc) h->qmap_dev = h->m_qmap;
-    const int32_t rc = wbc_step(h, flags);
-    h->qmap_dev = qm;
-    h->out_tau = bt; h->out_grf = bg; h->out_x = bx; h->out_status = bs; h->out_iters = bi;
-    h->in_pose = ip; h->in_nu = in; h->in_qj = iq; h->in_ref = ir; h->in_contacts = ic; h->in_switching = is;
+    const int32_t rc = zc ? step_on(h, flags, {h->m_in, h->m_out, h->m_qmap})
+                          : step_on(h, flags, {wbc::const_view(h->own_in), h->own_out, h->d_qmap});
     // zero-copy: the pinned blocks hold this cycle's inputs (and map) whether or not the step ran, and
     // the host-side mask count / map already describe them, so the own buffers follow them at the next
     // sync_own in either case (on a failed step too, so d_contacts never lags n_stance_own / h_qmap)
     h->zc_stale = zc;
     if (rc != WBC_OK) return rc;
     if (!zc)
-        WBC_HIP(hipMemcpyAsync(h->h_out, h->d_outblk, (flags & WBC_NO_X) ? outb - xb : outb, hipMemcpyDeviceToHost,
+        WBC_HIP(hipMemcpyAsync(h->h_out, h->d_outblk, wbc::output_block_bytes(B, !(flags & WBC_NO_X)), hipMemcpyDeviceToHost,
                                h->stream));
     return WBC_OK;
 }
@@ -997,26 +954,13 @@ int32_t resident_cycle(wbc_engine* h, uint32_t flags) {
         if (e != hipSuccess) return e;
         // the step reads the engine's own device input block (the wave copies the pinned block into it
         // every cycle) and writes the pinned output block through its device address
-        const double* ib = static_cast<const double*>(h->d_inblk);
-        double* ob = static_cast<double*>(h->m_out);
-        wbc::KernelArgs a = make_args(h, flags);
-        a.base_pose = ib;
-        a.nu = ib + B * WBC_POSE_LEN;
-        a.qj = a.nu + B * WBC_NU_LEN;
-        a.ref = a.qj + B * WBC_NUM_JOINTS;
-        a.contacts = reinterpret_cast<const uint8_t*>(a.ref + B * WBC_REF_LEN);
-        a.switching = a.contacts + B;
-        a.tau = ob;
-        a.grf = ob + B * WBC_NUM_JOINTS;
-        a.status = reinterpret_cast<int32_t*>(a.grf + B * WBC_NUM_JOINTS);
-        a.iters = a.status + B;
-        a.x = (flags & WBC_NO_X) ? nullptr : reinterpret_cast<double*>(a.iters + B);
+        wbc::KernelArgs a = make_args(h, flags, wbc::const_view(h->own_in), h->m_out);
         a.elim = 1;  // as begin_step16: the default step
         a.qmap = nullptr;  // one wave: its robots in batch order
         a.nwaves = 1;
         __atomic_store_n(&h->res_box->exited, 0ull, __ATOMIC_RELEASE);
-        const int words = (int)((in_block_bytes(B) + 7) / 8);
-        e = wbc_launch_resident(&a, h->res_box_dev, h->m_in, h->d_inblk, words, seq0, kResidentIdleTicks, h->res_stream);
+        e = wbc_launch_resident(&a, h->res_box_dev, h->m_in.pose, h->d_inblk, (int)wbc::input_block_words(B), seq0,
+                                kResidentIdleTicks, h->res_stream);
         if (e != hipSuccess) return e;
         h->res_on = true;
         h->res_flags = flags;
@@ -1061,22 +1005,12 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_cycle: mode hypotheses are set");
     if (!base_pose || !nu || !qj || !ref || !contacts || !switching) return fail(WBC_ERR_ARG, "wbc_cycle: null input");
-    if (h->in_rp && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
-        return fail(WBC_ERR_STATE, std::string("wbc_cycle: ") +
-                                       ((flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT") +
-                                       " with a per-robot parameter table in force (plain cycle only; clear it with "
-                                       "wbc_set_robot_params(h, NULL))");
-    if (h->in_cn && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
-        return fail(WBC_ERR_STATE, std::string("wbc_cycle: ") +
-                                       ((flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT") +
-                                       " with contact normals in force (plain cycle only; clear them with "
-                                       "wbc_set_contact_normals(h, NULL))");
+    if (const int32_t rc = refuse_tables(h, "wbc_cycle", flags, WBC_SPLIT | WBC_FUSED | WBC_RESIDENT, "plain cycle only")) return rc;
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
-    const size_t inb = in_block_bytes(B), outb = out_block_bytes(B);
     if (!h->h_in) {
-        WBC_HIP(hipHostMalloc(&h->h_in, (inb + 7) / 8 * 8, hipHostMallocMapped));  // (whole words: the resident copy)
-        WBC_HIP(hipHostMalloc(&h->h_out, outb, hipHostMallocMapped));
+        WBC_HIP(hipHostMalloc(&h->h_in, 8 * wbc::input_block_words(B), hipHostMallocMapped));  // (whole words: the resident copy)
+        WBC_HIP(hipHostMalloc(&h->h_out, wbc::output_block_bytes(B), hipHostMallocMapped));
 #ifndef WBC_CYCLE_COPY  // (A/B builds only: the copy cycle at every batch size)
         // Small batches (the B = 1 drop-in) run zero-copy: the step reads the pinned input block and
         // writes the pinned output block through their device addresses (a few hundred bytes over
@@ -1086,33 +1020,27 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
             if (hipHostGetDevicePointer(&mi, h->h_in, 0) == hipSuccess &&
                 hipHostGetDevicePointer(&mo, h->h_out, 0) == hipSuccess &&
                 hipHostGetDevicePointer(&mq, h->h_qmap, 0) == hipSuccess) {
-                h->m_in = mi;
-                h->m_out = mo;
+                h->m_in = wbc::input_view(static_cast<const void*>(mi), B);
+                h->m_out = wbc::output_view(mo, B);
                 h->m_qmap = static_cast<const int32_t*>(mq);
-                h->m_contacts = reinterpret_cast<const uint8_t*>(static_cast<const double*>(mi) +
-                                                                 B * (WBC_POSE_LEN + WBC_NU_LEN + WBC_NUM_JOINTS + WBC_REF_LEN));
             }
             (void)hipGetLastError();
         }
 #endif
     }
     // pack the host inputs in the device block's layout (pinned), one H2D copy
-    double* hp = static_cast<double*>(h->h_in);
-    std::memcpy(hp, base_pose, B * WBC_POSE_LEN * sizeof(double));
-    hp += B * WBC_POSE_LEN;
-    std::memcpy(hp, nu, B * WBC_NU_LEN * sizeof(double));
-    hp += B * WBC_NU_LEN;
-    std::memcpy(hp, qj, B * WBC_NUM_JOINTS * sizeof(double));
-    hp += B * WBC_NUM_JOINTS;
-    std::memcpy(hp, ref, B * WBC_REF_LEN * sizeof(double));
-    hp += B * WBC_REF_LEN;
-    std::memcpy(reinterpret_cast<uint8_t*>(hp), contacts, B);
-    std::memcpy(reinterpret_cast<uint8_t*>(hp) + B, switching, B);
+    const wbc::InputView hp = wbc::input_view(h->h_in, B);
+    std::memcpy(hp.pose, base_pose, B * WBC_POSE_LEN * sizeof(double));
+    std::memcpy(hp.nu, nu, B * WBC_NU_LEN * sizeof(double));
+    std::memcpy(hp.qj, qj, B * WBC_NUM_JOINTS * sizeof(double));
+    std::memcpy(hp.ref, ref, B * WBC_REF_LEN * sizeof(double));
+    std::memcpy(hp.contacts, contacts, B);
+    std::memcpy(hp.switching, switching, B);
     h->n_stance_own = count_stance(contacts, B);  // d_contacts holds these masks from here on
     h->qmap_waves = wbc::qmap_build(contacts, h->batch, h->h_qmap);  // uploaded by enqueue_cycle
     h->qmap_host = true;
     if (!x) flags |= WBC_NO_X;
-    if ((flags & WBC_RESIDENT) && h->m_in && B <= (size_t)wbc::QMAP_SEG && !(flags & (WBC_SPLIT | WBC_FUSED | WBC_DEBUG))) {
+    if ((flags & WBC_RESIDENT) && h->m_in.pose && B <= (size_t)wbc::QMAP_SEG && !(flags & (WBC_SPLIT | WBC_FUSED | WBC_DEBUG))) {
         const int32_t rc = resident_cycle(h, flags & ~WBC_RESIDENT);
         if (rc != WBC_OK) return rc;
     } else {
@@ -1121,14 +1049,12 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
         if (rc != WBC_OK) return rc;
         WBC_HIP(hipStreamSynchronize(h->stream));
     }
-    const size_t xb = B * WBC_NV * sizeof(double);
-    const double* o = static_cast<const double*>(h->h_out);
-    if (tau) std::memcpy(tau, o, B * WBC_NUM_JOINTS * sizeof(double));
-    if (grf) std::memcpy(grf, o + B * WBC_NUM_JOINTS, B * WBC_NUM_JOINTS * sizeof(double));
-    const int32_t* oi = reinterpret_cast<const int32_t*>(o + 2 * B * WBC_NUM_JOINTS);
-    if (status) std::memcpy(status, oi, B * sizeof(int32_t));
-    if (iters) std::memcpy(iters, oi + B, B * sizeof(int32_t));
-    if (x) std::memcpy(x, reinterpret_cast<const double*>(oi + 2 * B), xb);
+    const wbc::OutputView o = wbc::output_view(h->h_out, B);
+    if (tau) std::memcpy(tau, o.tau, B * WBC_NUM_JOINTS * sizeof(double));
+    if (grf) std::memcpy(grf, o.grf, B * WBC_NUM_JOINTS * sizeof(double));
+    if (status) std::memcpy(status, o.status, B * sizeof(int32_t));
+    if (iters) std::memcpy(iters, o.iters, B * sizeof(int32_t));
+    if (x) std::memcpy(x, o.x, B * WBC_NV * sizeof(double));
     return WBC_OK;
 }
 
@@ -1145,11 +1071,11 @@ int32_t wbc_get_output(wbc_engine* h, double* tau, double* grf, double* x, int32
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     hipStream_t st = h->stream;
-    if (tau) WBC_HIP(hipMemcpyAsync(tau, h->out_tau, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (grf) WBC_HIP(hipMemcpyAsync(grf, h->out_grf, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (x) WBC_HIP(hipMemcpyAsync(x, h->out_x, B * WBC_NV * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) WBC_HIP(hipMemcpyAsync(status, h->out_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (iters) WBC_HIP(hipMemcpyAsync(iters, h->out_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (tau) WBC_HIP(hipMemcpyAsync(tau, h->out.tau, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (grf) WBC_HIP(hipMemcpyAsync(grf, h->out.grf, B * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x) WBC_HIP(hipMemcpyAsync(x, h->out.x, B * WBC_NV * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (status) WBC_HIP(hipMemcpyAsync(status, h->out.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (iters) WBC_HIP(hipMemcpyAsync(iters, h->out.iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     WBC_HIP(hipStreamSynchronize(st));
     return WBC_OK;
 }
@@ -1158,11 +1084,11 @@ int32_t wbc_device_outputs(wbc_engine* h, double** d_tau, double** d_grf, double
                            int32_t** d_iters) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
-    if (d_tau) *d_tau = h->out_tau;
-    if (d_grf) *d_grf = h->out_grf;
-    if (d_x) *d_x = h->out_x;
-    if (d_status) *d_status = h->out_status;
-    if (d_iters) *d_iters = h->out_iters;
+    if (d_tau) *d_tau = h->out.tau;
+    if (d_grf) *d_grf = h->out.grf;
+    if (d_x) *d_x = h->out.x;
+    if (d_status) *d_status = h->out.status;
+    if (d_iters) *d_iters = h->out.iters;
     return WBC_OK;
 }
 

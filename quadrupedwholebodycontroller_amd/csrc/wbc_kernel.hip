@@ -1,9 +1,14 @@
 // wbc_kernel.hip — batched whole-body-control step for gfx950 (MI355X), fp64.
 //
-// (Three translation units include this file to build one kernel each under its own schedule:
-// wbc_kernel_stance.hip the stance-only default step, wbc_update_solve_kernel<0, true> (DESIGN.md
-// 4.22); wbc_kernel_step0.hip the stateless default step, wbc_update_solve_kernel<0>; and
-// wbc_kernel_modes.hip the mode loop, wbc_modes_kernel (4.24).  This file's own unit builds the rest.)
+// (Eleven translation units, wbc_kernel_<unit>.hip, include this file to build one kernel each under
+// its own schedule (Makefile KTU).  Nine hold one instance of the default
+// step each, wbc_update_solve_kernel<STF, SONLY, RP, CN>: stance, step0, step1 the plain ones
+// (stance-only, stateless, stateful), rps, rp0, rp1 the same under a per-robot parameter table (15),
+// cns, cn0, cn1 under per-robot contact normals (16).  Such a unit names its launcher and its four
+// template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
+// loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
+// wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
+// unit builds the rest: the split and fused forms, the wave map's builder, the reset.)
 // The default step (wbc_update_solve_kernel, the mode loop wbc_modes_kernel and the resident B <= 4
 // cycle wbc_resident_kernel) runs four robots per 64-lane wavefront, a 16-lane segment each, one
 // workgroup = one wave, one wave per SIMD (≈ 400 registers, 40 KB of LDS), and solves each robot's
@@ -4576,12 +4581,14 @@ struct SolveLds {
     QpScratch q;
 };
 
-// The one-kernel translation units (wbc_kernel_stance.hip, wbc_kernel_step0.hip,
-// wbc_kernel_modes.hip) include this file under their own macro, which keeps only their kernel and
-// its launcher; this file's own unit builds everything else
-#if defined(WBC_STANCE_TU) || defined(WBC_STEP0_TU) || defined(WBC_STEP1_TU) || defined(WBC_MODES_TU) || \
-    defined(WBC_RESIDENT_TU) || defined(WBC_RP0_TU) || defined(WBC_RP1_TU) || defined(WBC_RPS_TU) || \
-    defined(WBC_CN0_TU) || defined(WBC_CN1_TU) || defined(WBC_CNS_TU)
+// The one-kernel translation units (wbc_kernel_<unit>.hip) include this file under a macro that
+// keeps only their kernel and its launcher: WBC_STEP_INSTANCE (an instance of the default step, with
+// WBC_STEP_LAUNCHER), WBC_MODES_TU or WBC_RESIDENT_TU; this file's own unit builds everything else
+// 
+#if defined(WBC_STEP_INSTANCE) != defined(WBC_STEP_LAUNCHER)
+#error "a default-step unit defines both WBC_STEP_INSTANCE and WBC_STEP_LAUNCHER"
+#endif
+#if defined(WBC_STEP_INSTANCE) || defined(WBC_MODES_TU) || defined(WBC_RESIDENT_TU)
 #define WBC_SINGLE_TU 1
 #endif
 #ifndef WBC_SINGLE_TU
@@ -4690,8 +4697,13 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
 // kernel's arguments in its kernarg segment (passing the struct would pin a stack copy to the whole
 // kernel; a callee has no kernarg pointer of its own).
-// (One instance per calling kernel, TAG: a shared callee is allocated for the larger of its callers'
-// register budgets, which raised the default step's to 512 registers and its scratch to 2.2 KB.)
+// (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
+// larger of its callers' register budgets, which raised the default step's to 512 registers and its
+// scratch to 2.2 KB.  The values are part of the instances' symbol names.)
+enum FbKind { FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10 };
+constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
+constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
+constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
 __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base, const double* r, bool bad) {
@@ -4705,8 +4717,8 @@ __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base,
     pv.kd_swing = bad ? base.kd_swing : r[WBC_RP_KD_SWING];
     pv.slack_weight = bad ? base.slack_weight : r[WBC_RP_SLACK_WEIGHT];
 }
-// (TAG >= 6: the per-robot-parameter instances, KernelArgs::rp: each fallback QP is solved under its
-// own robot's row, as its reduction was attempted; TAG >= 10: the contact-normal instances, which
+// (fb_reads_rp: the per-robot-parameter instances, KernelArgs::rp: each fallback QP is solved under its
+// own robot's row, as its reduction was attempted; fb_reads_cn: the contact-normal instances, which
 // build the fallback QP's friction faces from its own row of KernelArgs::cn as well, build_normal<true>)
 template <int TAG>
 __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, unsigned long long fm, int qp,
@@ -4719,14 +4731,14 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
         const int seg = __builtin_ctzll(fm) / UPD_SUB;
         fm &= fm - 1ull;
         wsync();
-        if constexpr (TAG >= 6) {
+        if constexpr (fb_reads_rp(TAG)) {
             const double* r = f.rp + (size_t)__builtin_amdgcn_readlane(qp, seg * UPD_SUB) * WBC_RP_LEN;
             double rv[WBC_RP_LEN - 1];
 #pragma unroll
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
-        solve_general_qp<(TAG >= 10)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        solve_general_qp<fb_reads_cn(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -4876,7 +4888,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<(CN ? 10 : RP ? 6 : 2) + STF>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -4988,7 +5000,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_resident_kernel(KernelArgs args, ResidentBox* bo
         }
         const unsigned long long fm = __ballot(fb && lane == 0);
         if (fm)
-            drain_fallbacks<4 + STF>(ap, fm, qp,
+            drain_fallbacks<fb_tag(FB_RESIDENT, STF)>(ap, fm, qp,
                                      reinterpret_cast<SolveLds*>(&L));
         // outputs (pinned host memory) and history (HBM) stored, then the cycle published
         __syncthreads();
@@ -5028,7 +5040,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_modes_kernel(KernelArgs a) {
     for (int it = 0; it < M; ++it) {
         const unsigned long long fm = __ballot(wr && lane == 0 && ((fails >> it) & 1u));
         if (fm)
-            drain_fallbacks<1>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm,
+            drain_fallbacks<fb_tag(FB_MODES)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm,
                                row * K + a.mode_order[c * M + it], reinterpret_cast<SolveLds*>(&L));
     }
 }
@@ -5302,20 +5314,18 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 
 }  // namespace wbc
 
-#ifdef WBC_STANCE_TU
-// The stance-only default step (wbc_kernel_stance.hip): built in a translation unit of its own so
-// that its schedule can be chosen apart from the mixed-form kernel's (Makefile STANCE_KFLAGS)
-extern "C" hipError_t wbc_launch_stance_step(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful || a->modes || a->qmap) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_STEP0_TU)
-// The stateless default step of any mask mix (wbc_kernel_step0.hip: both forms, its own schedule,
-// Makefile STEP0_KFLAGS; wbc_launch_update_solve below forwards its stateless steps here)
-extern "C" hipError_t wbc_launch_update_solve0(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(wbc::wbc_update_solve_kernel<0>, dim3(a->nwaves), dim3(64), 0, st, *a);
+#ifdef WBC_STEP_INSTANCE
+// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN>, in a translation unit
+// of its own so that its schedule can be chosen apart from the other kernels' (Makefile <UNIT>_KFLAGS):
+// the unit file names the launcher and the four template arguments, the engine picks the launcher
+// (wbc_engine.cpp kStepLaunchers, wbc_layout.h step_instance).  The step in one launch: the update
+// kernel reducing and solving every QP inline, and the QPs whose reduction was not usable with the
+// general method in the same wave (drain_fallbacks: their records carry their own mask and bounds,
+// so the general solve runs them with modes = 0).
+extern "C" hipError_t WBC_STEP_LAUNCHER(const wbc::KernelArgs* a, hipStream_t st) {
+    static_assert(wbc::UPD_RPW == wbc::QMAP_SEG, "the wave map's segments are the kernel's");
+    if (wbc::step_args_refused(WBC_STEP_INSTANCE, *a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<WBC_STEP_INSTANCE>), dim3(a->nwaves), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 #elif defined(WBC_MODES_TU)
@@ -5323,14 +5333,6 @@ extern "C" hipError_t wbc_launch_update_solve0(const wbc::KernelArgs* a, hipStre
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st) {
     if (a->nwaves <= 0 || a->modes <= 0 || a->mloop <= 0 || a->modes % a->mloop != 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wbc::wbc_modes_kernel, dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_STEP1_TU)
-// The stateful default step (wbc_kernel_step1.hip, Makefile STEP1_KFLAGS; wbc_launch_update_solve
-// below forwards its stateful steps here)
-extern "C" hipError_t wbc_launch_update_solve1(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || !a->stateful) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(wbc::wbc_update_solve_kernel<1>, dim3(a->nwaves), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 #elif defined(WBC_RESIDENT_TU)
@@ -5358,56 +5360,7 @@ extern "C" hipError_t wbc_preload_resident() {
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&wbc::wbc_resident_kernel<0>));
     return e;
 }
-#elif defined(WBC_RP0_TU)
-// The default step under a per-robot parameter table (KernelArgs::rp), stateless, any mask mix
-// (wbc_kernel_rp0.hip, Makefile RP0_KFLAGS)
-extern "C" hipError_t wbc_launch_update_solve_rp0(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful || a->modes || !a->rp) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, false, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_RPS_TU)
-// The stance-only default step under a per-robot parameter table (wbc_kernel_rps.hip, Makefile
-// RPS_KFLAGS): stateless, every mask 15, as wbc_launch_stance_step
-extern "C" hipError_t wbc_launch_stance_step_rp(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful || a->modes || a->qmap || !a->rp) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_RP1_TU)
-// The stateful default step under a per-robot parameter table (wbc_kernel_rp1.hip, Makefile RP1_KFLAGS)
-extern "C" hipError_t wbc_launch_update_solve_rp1(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || !a->stateful || a->modes || !a->rp) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<1, false, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_CN0_TU)
-// The default step under per-robot contact normals (KernelArgs::cn, with KernelArgs::rp), stateless,
-// any mask mix, all-stance steps included (wbc_kernel_cn0.hip, Makefile CN0_KFLAGS)
-extern "C" hipError_t wbc_launch_update_solve_cn0(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful || a->modes || !a->rp || !a->cn) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, false, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_CNS_TU)
-// The stance-only default step under per-robot contact normals (wbc_kernel_cns.hip, Makefile
-// CNS_KFLAGS): stateless, every mask 15, as wbc_launch_stance_step_rp
-extern "C" hipError_t wbc_launch_stance_step_cn(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || a->stateful || a->modes || a->qmap || !a->rp || !a->cn) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<0, true, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
-#elif defined(WBC_CN1_TU)
-// The stateful default step under per-robot contact normals (wbc_kernel_cn1.hip, Makefile CN1_KFLAGS)
-extern "C" hipError_t wbc_launch_update_solve_cn1(const wbc::KernelArgs* a, hipStream_t st) {
-    if (a->nwaves <= 0 || !a->stateful || a->modes || !a->rp || !a->cn) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<1, false, true, true>), dim3(a->nwaves), dim3(64), 0, st, *a);
-    return hipGetLastError();
-}
 #else
-extern "C" hipError_t wbc_launch_update_solve0(const wbc::KernelArgs* a, hipStream_t st);
-extern "C" hipError_t wbc_launch_update_solve1(const wbc::KernelArgs* a, hipStream_t st);
-
 // Launchers used by the engine (wbc_engine.cpp); grid = one 64-lane workgroup per robot.
 extern "C" hipError_t wbc_launch_step(const wbc::KernelArgs* a, hipStream_t st) {
     hipLaunchKernelGGL(wbc::wbc_step_kernel, dim3(a->batch), dim3(64), 0, st, *a);
@@ -5438,14 +5391,6 @@ extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStrea
     hipLaunchKernelGGL(wbc::wbc_solve_stance_kernel, dim3(a->batch), dim3(64), 0, st, *a);
     hipLaunchKernelGGL(wbc::wbc_solve_fallback_kernel, dim3(16), dim3(64), 0, st, *a);
     return hipGetLastError();
-}
-// The default step in one launch: the update kernel reducing and solving every QP inline, and the
-// QPs whose reduction was not usable with the general method in the same wave (drain_fallbacks:
-// their records carry their own mask and bounds, so the general solve runs them with modes = 0).
-extern "C" hipError_t wbc_launch_update_solve(const wbc::KernelArgs* a, hipStream_t st) {
-    static_assert(wbc::UPD_RPW == wbc::QMAP_SEG, "the wave map's segments are the kernel's");
-    if (a->nwaves <= 0) return hipErrorInvalidValue;
-    return a->stateful ? wbc_launch_update_solve1(a, st) : wbc_launch_update_solve0(a, st);
 }
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st) {
     hipLaunchKernelGGL(wbc::wbc_reset_kernel, dim3(batch), dim3(64), 0, st, hist, mask, batch);

@@ -1,7 +1,8 @@
 // wbc_kernel_cn1.hip — the stateful default step under per-robot contact normals
 // (wbc_update_solve_kernel<1, false, true, true>, KernelArgs::cn: wbc_set_contact_normals /
 // wbc_bind_device_contact_normals).  A translation unit of its
-// own (Makefile CN1_KFLAGS); the code is wbc_kernel.hip's, which WBC_CN1_TU limits to this one kernel
+// own (Makefile CN1_KFLAGS); the code is wbc_kernel.hip's, which WBC_STEP_INSTANCE limits to this one kernel
 // and its launcher.
-#define WBC_CN1_TU 1
+#define WBC_STEP_LAUNCHER wbc_launch_update_solve_cn1
+#define WBC_STEP_INSTANCE 1, false, true, true  // STF, SONLY, RP, CN
 #include "wbc_kernel.hip"

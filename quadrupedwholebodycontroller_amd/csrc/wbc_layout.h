@@ -221,6 +221,86 @@ WBC_HD inline int rp_bad_column(const double* r) {
     }
     return -1;
 }
+// The arguments an instance wbc_update_solve_kernel<STF, SONLY, RP, CN> of the default step refuses
+// (its unit's launcher, wbc_kernel.hip): a step without waves; a stateful step for a stateless
+// instance or the reverse; mode hypotheses or a wave map for a stance-only instance (every QP mask
+// 15, in batch order); mode hypotheses or no table for a per-robot-parameter instance; no normals
+// for a contact-normal instance.
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a) {
+    if (a.nwaves <= 0 || (a.stateful != 0) != (STF != 0)) return true;
+    if (SONLY && (a.modes || a.qmap)) return true;
+    if (RP && (a.modes || !a.rp)) return true;
+    return CN && !a.cn;
+}
+// The default step's instances, one kernel unit each (wbc_kernel_<unit>.hip): per table in force
+// (none, parameters, parameters + normals) the stateless instance of any mask mix, the stateful one,
+// the stance-only one.  The one list names the instances (STEP_<unit>) and, in the engine, orders the
+// launcher table that StepInstance indexes (wbc_engine.cpp kStepLaunchers).  step_instance: the one
+// a step takes.  Normals come with a parameter table (the caller's or the engine's uniform one), so
+// cn wins over rp; all_stance (wbc_engine.cpp step_all_stance: stateless, every mask 15, no map, no
+// hypotheses) never comes with stateful.
+#define WBC_STEP_UNITS(X) X(step0) X(step1) X(stance) X(rp0) X(rp1) X(rps) X(cn0) X(cn1) X(cns)
+enum StepInstance {
+#define X(unit) STEP_##unit,
+    WBC_STEP_UNITS(X)
+#undef X
+    STEP_INSTANCES
+};
+constexpr StepInstance step_instance(bool cn, bool rp, bool all_stance, bool stateful) {
+    return all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
+         : stateful   ? (cn ? STEP_cn1 : rp ? STEP_rp1 : STEP_step1)
+                      : (cn ? STEP_cn0 : rp ? STEP_rp0 : STEP_step0);
+}
+
+// The packed blocks of a control cycle (wbc_cycle; the engine's own device buffers have the same
+// layout, so a host cycle is one copy each way): inputs [pose | nu | qj | ref | contacts | switching],
+// outputs [tau | grf | status | iters | x].  The views give the arrays of a block for B robots at
+// `base` (8-byte aligned); status + iters are 8 bytes per robot, so x stays 8-byte aligned, and x is
+// last, so a cycle without it copies the block's head.
+template <class D, class U>
+struct InputViewT {
+    D *pose, *nu, *qj, *ref;
+    U *contacts, *switching;
+};
+using InputView = InputViewT<double, uint8_t>;
+using ConstInputView = InputViewT<const double, const uint8_t>;
+struct OutputView {
+    double *tau, *grf;
+    int32_t *status, *iters;
+    double* x;
+};
+template <class D, class U, class V>
+inline InputViewT<D, U> input_view_at(V* base, size_t B) {
+    InputViewT<D, U> v;
+    v.pose = static_cast<D*>(base);
+    v.nu = v.pose + B * WBC_POSE_LEN;
+    v.qj = v.nu + B * WBC_NU_LEN;
+    v.ref = v.qj + B * WBC_NUM_JOINTS;
+    v.contacts = reinterpret_cast<U*>(v.ref + B * WBC_REF_LEN);
+    v.switching = v.contacts + B;
+    return v;
+}
+inline InputView input_view(void* base, size_t B) { return input_view_at<double, uint8_t>(base, B); }
+inline ConstInputView input_view(const void* base, size_t B) { return input_view_at<const double, const uint8_t>(base, B); }
+inline ConstInputView const_view(const InputView& v) { return {v.pose, v.nu, v.qj, v.ref, v.contacts, v.switching}; }
+inline OutputView output_view(void* base, size_t B) {
+    OutputView v;
+    v.tau = static_cast<double*>(base);
+    v.grf = v.tau + B * WBC_NUM_JOINTS;
+    v.status = reinterpret_cast<int32_t*>(v.grf + B * WBC_NUM_JOINTS);
+    v.iters = v.status + B;
+    v.x = reinterpret_cast<double*>(v.iters + B);
+    return v;
+}
+inline size_t input_block_bytes(size_t B) {
+    return B * (WBC_POSE_LEN + WBC_NU_LEN + WBC_NUM_JOINTS + WBC_REF_LEN) * sizeof(double) + 2 * B;
+}
+// (in whole 8-byte words, as the block is allocated: the resident cycle copies it by words)
+inline size_t input_block_words(size_t B) { return (input_block_bytes(B) + 7) / 8; }
+inline size_t output_block_bytes(size_t B, bool with_x = true) {
+    return B * 2 * WBC_NUM_JOINTS * sizeof(double) + 2 * B * sizeof(int32_t) + (with_x ? B * WBC_NV * sizeof(double) : 0);
+}
+
 // The ground normal m of one foot (three doubles of a wbc.h WBC_CN_LEN row) the step accepts: finite,
 // 0.25 <= |m|^2 <= 4, m_z / |m| >= 0.5.  One definition for the host's validation
 // (wbc_set_contact_normals) and the kernels' (a device-bound row); cn_bad_foot: -1, or the first

@@ -1,0 +1,308 @@
+"""GPU: what the engine's shared host code must keep: the one table type behind the
+per-robot parameters and the contact normals, the one refusal of the forms that do not read them, the
+one launcher table of the default step, and the cycle that no longer borrows the handle's bindings.
+
+* every refusal's wbc_last_error() text, letter for letter as the engine wrote it out per call and per
+  table before the refusals were shared (recorded with that build of the library);
+* the precedence of the tables (a caller's bound device table, else the engine's own, else none), step
+  by step through set / bind / clear, by read-back and by the bits of a default step;
+* caller-bound device inputs and outputs across a wbc_cycle, zero-copy, copying and resident;
+* each of the nine instances of the default step is reached and gives the plain engine's bits."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import contact_normals_oracle as CN
+from quadrupedwholebodycontroller_amd import FUSED, RESIDENT, SPLIT, STATELESS, Engine, WbcError, workloads
+from test_gpu_robot_params import table as rp_table
+
+pytestmark = pytest.mark.gpu
+
+KEYS = ("tau", "grf", "x", "status", "iters")
+ERR_ARG, ERR_STATE = -1, -3
+
+
+def load(e, inp):
+    e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
+    e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
+
+
+def cycle(e, inp, flags):
+    return e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
+
+
+def assert_identical(a, b, what=""):
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), (what, k)
+
+
+def cn_table(B, seed):
+    return np.ascontiguousarray(CN.normals(B, seed, 0.35).reshape(B, 12))
+
+
+def last_error(e):
+    return e.lib.wbc_last_error().decode()
+
+
+# --- refusal texts ----------------------------------------------------------------------------------
+RP_IS = "a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))"
+CN_ARE = "contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))"
+RP_WITH = " with a per-robot parameter table in force ({}; clear it with wbc_set_robot_params(h, NULL))"
+CN_WITH = " with contact normals in force ({}; clear them with wbc_set_contact_normals(h, NULL))"
+REFUSALS = {
+    "rp": {
+        "update": "wbc_update: " + RP_IS,
+        "solve": "wbc_solve: " + RP_IS,
+        "step_split": "wbc_step: WBC_SPLIT" + RP_WITH.format("default form only"),
+        "step_fused": "wbc_step: WBC_FUSED" + RP_WITH.format("default form only"),
+        "step_modes": "wbc_step_modes: " + RP_IS,
+        "cycle_split": "wbc_cycle: WBC_SPLIT" + RP_WITH.format("plain cycle only"),
+        "cycle_fused": "wbc_cycle: WBC_FUSED" + RP_WITH.format("plain cycle only"),
+        "cycle_resident": "wbc_cycle: WBC_RESIDENT" + RP_WITH.format("plain cycle only"),
+    },
+    "cn": {
+        "update": "wbc_update: " + CN_ARE,
+        "solve": "wbc_solve: " + CN_ARE,
+        "step_split": "wbc_step: WBC_SPLIT" + CN_WITH.format("default form only"),
+        "step_fused": "wbc_step: WBC_FUSED" + CN_WITH.format("default form only"),
+        "step_modes": "wbc_step_modes: " + CN_ARE,
+        "cycle_split": "wbc_cycle: WBC_SPLIT" + CN_WITH.format("plain cycle only"),
+        "cycle_fused": "wbc_cycle: WBC_FUSED" + CN_WITH.format("plain cycle only"),
+        "cycle_resident": "wbc_cycle: WBC_RESIDENT" + CN_WITH.format("plain cycle only"),
+    },
+}
+# written out once in full, so that the pieces above are checked against a whole sentence too
+assert REFUSALS["rp"]["cycle_resident"] == ("wbc_cycle: WBC_RESIDENT with a per-robot parameter table in force (plain cycle only; "
+                                            "clear it with wbc_set_robot_params(h, NULL))")
+assert REFUSALS["cn"]["step_modes"] == ("wbc_step_modes: contact normals are in force (default wbc_step only; clear them with "
+                                        "wbc_set_contact_normals(h, NULL))")
+
+
+@pytest.mark.parametrize("tables", ["rp", "cn", "both"])
+def test_refusal_texts(tables):
+    """B = 4.  With both tables in force the parameter table is the one named; with mode hypotheses set
+    the calls that do not take them say so first."""
+    B = 4
+    inp = workloads.rl_random(B, seed=91)
+    e = Engine(B)
+    load(e, inp)
+    if tables in ("rp", "both"):
+        e.set_robot_params(rp_table(B))
+    if tables in ("cn", "both"):
+        e.set_contact_normals(cn_table(B, 5))
+    want = REFUSALS["cn" if tables == "cn" else "rp"]
+    calls = {
+        "update": lambda: e.update(STATELESS),
+        "solve": lambda: e.solve(STATELESS),
+        "step_split": lambda: e.step(STATELESS | SPLIT),
+        "step_fused": lambda: e.step(STATELESS | FUSED),
+        "cycle_split": lambda: cycle(e, inp, STATELESS | SPLIT),
+        "cycle_fused": lambda: cycle(e, inp, STATELESS | FUSED),
+        "cycle_resident": lambda: cycle(e, inp, STATELESS | RESIDENT),
+    }
+    for name, call in calls.items():
+        with pytest.raises(WbcError) as ei:
+            call()
+        assert last_error(e) == want[name], name
+        assert f"({ERR_STATE})" in str(ei.value), name
+    e.set_modes([15, 5])
+    with pytest.raises(WbcError) as ei:
+        e.step_modes(STATELESS)
+    assert last_error(e) == want["step_modes"] and f"({ERR_STATE})" in str(ei.value)
+    for call, text in ((lambda: e.update(STATELESS), "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))"),
+                       (lambda: e.step(STATELESS | SPLIT), "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))"),
+                       (lambda: cycle(e, inp, STATELESS | RESIDENT), "wbc_cycle: mode hypotheses are set")):
+        with pytest.raises(WbcError):
+            call()
+        assert last_error(e) == text
+    e.close()
+
+
+def test_validation_texts():
+    """The host's refusal of a row names the row and the column (parameters) or the foot (normals); the
+    table in force stays."""
+    B = 4
+    e = Engine(B)
+    good_rp, good_cn = rp_table(B), cn_table(B, 5)
+    e.set_robot_params(good_rp)
+    e.set_contact_normals(good_cn)
+    bad = good_rp.copy()
+    bad[2, 0] = -1.0
+    with pytest.raises(WbcError) as ei:
+        e.set_robot_params(bad)
+    assert f"({ERR_ARG})" in str(ei.value)
+    assert last_error(e) == ("wbc_set_robot_params: row 2, column 0 (friction) = -1: need finite entries, friction >= 0, "
+                             "max_torque >= 0, slack_weight > 0")
+    bad = good_cn.copy()
+    bad[1, 6:9] = (0.0, 0.0, -1.0)
+    # (through the C entry point: the Python wrapper validates the same rule before it)
+    rc = e.lib.wbc_set_contact_normals(e.h, bad.ctypes.data_as(C.c_void_p))
+    assert rc == ERR_ARG
+    assert last_error(e) == ("wbc_set_contact_normals: row 1, foot 2 (RF) = (0, 0, -1): need finite entries, "
+                             "0.25 <= |m|^2 <= 4 and m_z / |m| >= 0.5")
+    assert np.array_equal(e.robot_params(), good_rp) and np.array_equal(e.contact_normals(), good_cn)
+    e.close()
+
+
+# --- table precedence ---------------------------------------------------------------------------------
+class Table:
+    """The calls of one of the two tables, and three tables of it."""
+
+    def __init__(self, kind, B):
+        self.kind = kind
+        if kind == "rp":
+            self.tables = [rp_table(B, seed) for seed in (7, 8, 9)]
+        else:
+            self.tables = [cn_table(B, seed) for seed in (5, 6, 7)]
+
+    def set(self, e, t):
+        (e.set_robot_params if self.kind == "rp" else e.set_contact_normals)(t)
+
+    def bind(self, e, t):
+        (e.bind_device_robot_params if self.kind == "rp" else e.bind_device_contact_normals)(t)
+
+    def get(self, e):
+        return e.robot_params() if self.kind == "rp" else e.contact_normals()
+
+
+@pytest.mark.parametrize("kind", ["rp", "cn"])
+def test_table_precedence(kind):
+    """none -> set own -> bind device -> clear own -> set own again -> unbind -> clear: after each, the
+    table read back is the caller's if bound, else the own one if set, else the defaults, and a default
+    step gives the bits of an engine that was handed that table directly.  A misaligned bind is refused
+    and changes nothing."""
+    import torch
+
+    B = 4
+    T = Table(kind, B)
+    own1, dev, own2 = T.tables
+    inp = workloads.rl_random(B, seed=91)
+
+    def direct(t):
+        e = Engine(B)
+        load(e, inp)
+        if t is not None:
+            T.set(e, t)
+        back = T.get(e)
+        e.step(STATELESS)
+        out = e.outputs()
+        e.close()
+        return back, out
+
+    want = {name: direct(t) for name, t in (("none", None), ("own1", own1), ("dev", dev), ("own2", own2))}
+    assert not np.array_equal(want["none"][1]["tau"], want["own1"][1]["tau"])
+    assert not np.array_equal(want["dev"][1]["tau"], want["own2"][1]["tau"])
+    assert np.array_equal(want["own1"][0], own1) and np.array_equal(want["dev"][0], dev)
+    d_dev = torch.from_numpy(dev).cuda()
+    # a 16-byte aligned tensor, then the same storage 8 bytes on
+    d_odd = torch.zeros(dev.size + 2, dtype=torch.float64, device="cuda")
+    assert d_odd.data_ptr() % 16 == 0
+    e = Engine(B)
+    load(e, inp)
+
+    def check(name, what):
+        assert np.array_equal(T.get(e), want[name][0]), what
+        e.step(STATELESS)
+        assert_identical(e.outputs(), want[name][1], what)
+
+    check("none", "at creation")
+    T.set(e, own1)
+    check("own1", "own table set")
+    with pytest.raises(WbcError) as ei:
+        T.bind(e, d_odd.data_ptr() + 8)
+    assert f"({ERR_ARG})" in str(ei.value) and "16-byte aligned" in str(ei.value)
+    check("own1", "after a refused bind")
+    T.bind(e, d_dev)
+    check("dev", "device table bound over the own one")
+    T.set(e, None)
+    check("dev", "own table cleared under a bound one")
+    T.set(e, own2)
+    check("dev", "own table set again under a bound one")
+    T.bind(e, 0)
+    check("own2", "unbound: the own table")
+    T.set(e, None)
+    check("none", "cleared")
+    e.close()
+
+
+# --- bindings across a cycle --------------------------------------------------------------------------
+@pytest.mark.parametrize("B,flags", [(4, 0), (4, RESIDENT), (65, 0)])
+def test_bindings_survive_a_cycle(B, flags):
+    """Caller-owned device inputs and outputs stay bound across wbc_cycle (B = 4: the zero-copy cycle
+    and the resident one; B = 65: the copying cycle, just past the zero-copy limit): the cycle reads its
+    own host arrays and returns a step on them, the next plain step reads the caller's inputs again and
+    writes the caller's buffers with the first step's bits."""
+    import torch
+
+    a, b = workloads.rl_random(B, seed=61), workloads.rl_random(B, seed=62)
+    want = {}
+    for name, inp in (("a", a), ("b", b)):
+        r = Engine(B)
+        load(r, inp)
+        r.step(STATELESS)
+        want[name] = r.outputs()
+        r.close()
+    assert not np.array_equal(want["a"]["tau"], want["b"]["tau"])
+    d_in = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in a.items()}
+    d_out = dict(tau=torch.zeros(B, 12, dtype=torch.float64, device="cuda"),
+                 grf=torch.zeros(B, 12, dtype=torch.float64, device="cuda"),
+                 x=torch.zeros(B, 42, dtype=torch.float64, device="cuda"),
+                 status=torch.full((B,), -1, dtype=torch.int32, device="cuda"),
+                 iters=torch.full((B,), -1, dtype=torch.int32, device="cuda"))
+    e = Engine(B)
+    e.bind_device_inputs(*(d_in[k].data_ptr() for k in ("base_pose", "nu", "qj", "ref", "contacts", "switching")))
+    e.bind_device_outputs(*(d_out[k].data_ptr() for k in KEYS))
+
+    def caller_buffers():
+        e.synchronize()
+        return {k: d_out[k].cpu().numpy() for k in KEYS}
+
+    e.step(STATELESS)
+    assert_identical(caller_buffers(), want["a"], "first step")
+    for t in d_out.values():
+        t.fill_(-1)
+    torch.cuda.synchronize()
+    got_b = cycle(e, b, STATELESS | flags)
+    assert_identical(got_b, want["b"], "the cycle")
+    after = caller_buffers()
+    for k in KEYS:  # the cycle wrote none of the caller's buffers
+        assert np.all(after[k] == -1), k
+    e.step(STATELESS)
+    assert_identical(caller_buffers(), want["a"], "the step after the cycle")
+    assert e.device_outputs() == {k: d_out[k].data_ptr() for k in KEYS}
+    e.close()
+
+
+# --- the nine instances -------------------------------------------------------------------------------
+@pytest.mark.parametrize("step", ["all_stance", "mixed", "stateful"])
+def test_each_instance_is_reached(step):
+    """B = 5: two waves, the second ragged.  Under no table, a uniform parameter table and flat normals,
+    an all-stance stateless step, a mixed-mask stateless step and a stateful step each give the plain
+    engine's bits (the table instances compute the same by design, so this shows that no cell of the
+    launcher table is empty or refuses; that the right cell is chosen is tests/test_step_dispatch.py's)."""
+    B = 5
+    inp = workloads.stance_cold(B, seed=7) if step == "all_stance" else workloads.rl_random(B, seed=7)
+    if step == "all_stance":
+        assert np.all(inp["contacts"] == 15)
+    else:
+        assert len(set(inp["contacts"].tolist())) > 1
+    flags = 0 if step == "stateful" else STATELESS
+    outs = {}
+    for tables in ("plain", "rp", "cn"):
+        e = Engine(B)
+        load(e, inp)
+        if tables == "rp":
+            e.set_robot_params(e.robot_params())  # the engine-wide values in every row
+        if tables == "cn":
+            e.set_contact_normals((0.0, 0.0, 1.0))
+        e.step(flags)
+        outs[tables] = e.outputs()
+        if step == "stateful":  # a second step, on the history the first one left
+            e.step(flags)
+            outs[tables + "2"] = e.outputs()
+        e.close()
+    for tables in ("rp", "cn"):
+        assert_identical(outs[tables], outs["plain"], (step, tables))
+        if step == "stateful":
+            assert_identical(outs[tables + "2"], outs["plain2"], (step, tables, "second step"))
