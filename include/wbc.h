@@ -325,6 +325,47 @@ int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table);
  * for every foot. */
 int32_t wbc_get_contact_normals(wbc_engine* h, double* table);
 
+/* Per-robot base body (a payload on the trunk; randomised mass, CoM and inertia): a table of doubles,
+ * row-major [B][WBC_BB_LEN], row b for robot b.  Rows are 112 bytes, so a table that starts 16-byte
+ * aligned keeps every row 16-byte aligned (required of a device-bound table).  Robot b is the engine's
+ * model with its base body (wbc_model::base_mass, base_com, base_inertia) replaced by row b; link
+ * bodies, joint frames and feet are the model's.  The total mass, the CoM, the centroidal inertia and
+ * the bias forces follow from the row; the mass of the desired wrench's gravity term is
+ *     model.total_mass + (row.mass - model.base_mass),
+ * so the model's own base as a row (what wbc_get_base_body returns without a table) gives the plain
+ * step bit for bit.  A row is valid when columns 0-12 are finite, mass > 0, the inertia is symmetric
+ * to 1e-9 of its trace and its symmetric part is positive definite. */
+enum {
+    WBC_BB_MASS = 0,    /* wbc_model::base_mass [kg] */
+    WBC_BB_COM = 1,     /* base_com[3], base frame [m] */
+    WBC_BB_INERTIA = 4, /* base_inertia[9], about the CoM, base axes, row-major [kg m^2] */
+    /* 13: reserved (ignored on input, written as 0 by wbc_get_base_body) */
+    WBC_BB_LEN = 14
+};
+/* Host table, validated and then copied on the engine stream (the call synchronizes it, so the
+ * caller may reuse the array).  An invalid row returns WBC_ERR_ARG, wbc_last_error names the row and
+ * the column, and the table in force before the call stays in force.  NULL clears the table: back to
+ * the model's base.
+ * While a base-body table is in force (this one or a device-bound one), with or without the other
+ * two tables:
+ *  - supported: wbc_step in its default form (stateless, stateful and WBC_COLD; with WBC_DEBUG,
+ *    WBC_NO_X, WBC_TIMED and WBC_GROUP) and plain wbc_cycle.  A row may change between stateful
+ *    cycles: the finite differences of the next cycle then see the change exactly as the reference's
+ *    would see a changed model (its history holds the previous cycle's T and Jbar, not the model).
+ *  - refused with WBC_ERR_STATE (wbc_last_error names the call or flag): wbc_update, wbc_solve,
+ *    wbc_step_modes, and wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT.  These
+ *    forms compute with the model's base only; they run as before once the table is cleared
+ *    (wbc_set_base_body(h, NULL) and no device table bound). */
+int32_t wbc_set_base_body(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_BB_LEN] (no copy, no host validation; the step reads the pointer
+ * directly).  NULL restores the engine-owned table of wbc_set_base_body, or none if none was set.  On
+ * the device an invalid row gives that robot WBC_QP_NUMERIC and zero outputs, as a non-finite input
+ * does; no other robot is touched. */
+int32_t wbc_bind_device_base_body(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_BB_LEN] to the host (synchronous); without one, the model's base in
+ * every row.  Column 13 is written as 0. */
+int32_t wbc_get_base_body(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

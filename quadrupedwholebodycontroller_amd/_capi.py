@@ -23,10 +23,16 @@ RP_LEN = 10
 # the per-robot contact-normal table (WBC_CN_LEN in include/wbc.h): three doubles per foot, legs LH, LF, RF, RH
 CN_LEN = 12
 FOOT_NAMES = ("LH", "LF", "RF", "RH")
+# the per-robot base-body table (WBC_BB_* in include/wbc.h): mass, com[3] (base frame), inertia[9] (about
+# the CoM, base axes, row-major), one reserved
+BB_LEN = 14
+BB_MASS, BB_COM, BB_INERTIA = 0, 1, 4
+BASE_BODY_NAMES = ("mass", "com", "inertia")
+BB_COLUMN_NAMES = ("mass", "com_x", "com_y", "com_z", "I_xx", "I_xy", "I_xz", "I_yx", "I_yy", "I_yz", "I_zx", "I_zy", "I_zz")
 
 # the per-robot tables of the default step: name -> row length; the C entry points of table <name> are
 # wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
-TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN}
+TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN}
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
 
 # WBC_DBG_* offsets (include/wbc.h)
@@ -206,6 +212,108 @@ def contact_normal_table(batch: int, normals) -> np.ndarray:
     return np.ascontiguousarray(t.reshape(B, CN_LEN))
 
 
+def base_body_row(model: WbcModel) -> np.ndarray:
+    """The model's own base body as a (BB_LEN,) row: what wbc_get_base_body returns without a table."""
+    row = np.zeros(BB_LEN)
+    row[BB_MASS] = model.base_mass
+    row[BB_COM:BB_COM + 3] = list(model.base_com)
+    row[BB_INERTIA:BB_INERTIA + 9] = list(model.base_inertia)
+    return row
+
+
+def base_body_bad_entry(row) -> int:
+    """The validity rule of one base-body row (wbc_layout.h bb_bad_entry): -1, or the first failing column."""
+    r = np.asarray(row, np.float64)
+    for c in range(BB_LEN - 1):
+        if not np.isfinite(r[c]):
+            return c
+    if not r[BB_MASS] > 0.0:
+        return BB_MASS
+    I = r[BB_INERTIA:BB_INERTIA + 9]
+    tol = 1e-9 * abs(I[0] + I[4] + I[8])
+    for lo, hi in ((1, 3), (2, 6), (5, 7)):
+        if not abs(I[lo] - I[hi]) <= tol:
+            return BB_INERTIA + lo
+    a, d, f = I[0], I[4], I[8]
+    b, c, e = 0.5 * (I[1] + I[3]), 0.5 * (I[2] + I[6]), 0.5 * (I[5] + I[7])
+    if not a > 0.0:
+        return BB_INERTIA
+    if not a * d - b * b > 0.0:
+        return BB_INERTIA + 4
+    if not a * (d * f - e * e) - b * (b * f - e * c) + c * (b * e - d * c) > 0.0:
+        return BB_INERTIA + 8
+    return -1
+
+
+def base_body_table(batch: int, model: WbcModel, table) -> np.ndarray:
+    """The [B, BB_LEN] table of wbc_set_base_body from a (B, 14) array, one (14,) row broadcast to all
+    robots, or a dict of BASE_BODY_NAMES -> one value or per-robot values (mass: scalar or (B,); com: (3,)
+    or (B, 3); inertia: (3, 3), (9,), (B, 3, 3) or (B, 9)), whose missing entries take the model's base.
+    Validated as the engine validates it (finite, mass > 0, inertia symmetric to 1e-9 of its trace and
+    positive definite); ValueError names the row and the column.  The reserved column is 0."""
+    B = int(batch)
+    out = np.tile(base_body_row(model), (B, 1))
+    if isinstance(table, dict):
+        unknown = sorted(set(table) - set(BASE_BODY_NAMES))
+        if unknown:
+            raise ValueError(f"unknown base body entries {unknown}; entries are {BASE_BODY_NAMES}")
+        if "mass" in table:
+            v = np.asarray(table["mass"], np.float64)
+            if v.shape not in ((), (B,)):
+                raise ValueError(f"base body mass: need a scalar or {B} values, got shape {v.shape}")
+            out[:, BB_MASS] = v
+        if "com" in table:
+            v = np.asarray(table["com"], np.float64)
+            if v.shape not in ((3,), (B, 3)):
+                raise ValueError(f"base body com: need shape (3,) or ({B}, 3), got {v.shape}")
+            out[:, BB_COM:BB_COM + 3] = v
+        if "inertia" in table:
+            v = np.asarray(table["inertia"], np.float64)
+            if v.shape not in ((3, 3), (9,), (B, 3, 3), (B, 9)):
+                raise ValueError(f"base body inertia: need shape (3, 3), (9,), ({B}, 3, 3) or ({B}, 9), got {v.shape}")
+            out[:, BB_INERTIA:BB_INERTIA + 9] = v.reshape(-1, 9)
+    else:
+        t = np.asarray(table, np.float64)
+        if t.shape not in ((BB_LEN,), (B, BB_LEN)):
+            raise ValueError(f"base body table: need shape ({B}, {BB_LEN}) or ({BB_LEN},), got {t.shape}")
+        out[:, :] = t
+    out[:, BB_LEN - 1] = 0.0
+    for b in range(B):
+        c = base_body_bad_entry(out[b])
+        if c >= 0:
+            raise ValueError(f"base body: row {b}, column {c} ({BB_COLUMN_NAMES[c]}) = {out[b, c]:g}: need finite entries, "
+                             "mass > 0 and a symmetric (to 1e-9 of its trace), positive definite inertia")
+    return out
+
+
+def base_body_with_payload(model: WbcModel, mass, position, inertia=None) -> np.ndarray:
+    """Base-body rows for a payload rigidly fixed to the trunk: a body of `mass` (scalar or (N,)) with its
+    CoM at `position` ((3,) or (N, 3), base frame) and inertia `inertia` about its own CoM in base axes
+    ((3, 3) or (N, 3, 3); None: a point mass).  The composite with the model's base, by the parallel-axis
+    theorem about the composite CoM:
+        M = m0 + mp,   c = c0 + (mp / M) (p - c0),   I = I0 + Ip + (m0 mp / M) (|d|^2 1 - d d^T),  d = p - c0.
+    Returns (N, BB_LEN), or (BB_LEN,) for one payload; zero mass gives the model's own row bit for bit."""
+    mp = np.asarray(mass, np.float64)
+    p = np.asarray(position, np.float64)
+    single = mp.ndim == 0 and p.ndim == 1 and (inertia is None or np.ndim(inertia) == 2)
+    N = max([1] + [v.shape[0] for v, nd in ((mp, 1), (p, 2)) if v.ndim == nd]
+            + ([np.shape(inertia)[0]] if inertia is not None and np.ndim(inertia) == 3 else []))
+    mp = np.broadcast_to(mp, (N,))
+    p = np.broadcast_to(p, (N, 3))
+    Ip = np.zeros((N, 3, 3)) if inertia is None else np.broadcast_to(np.asarray(inertia, np.float64), (N, 3, 3))
+    base = base_body_row(model)
+    m0, c0, I0 = base[BB_MASS], base[BB_COM:BB_COM + 3], base[BB_INERTIA:BB_INERTIA + 9].reshape(3, 3)
+    M = m0 + mp
+    d = p - c0
+    mu = m0 * mp / M
+    pa = (d * d).sum(axis=1)[:, None, None] * np.eye(3) - d[:, :, None] * d[:, None, :]
+    out = np.zeros((N, BB_LEN))
+    out[:, BB_MASS] = M
+    out[:, BB_COM:BB_COM + 3] = c0 + (mp / M)[:, None] * d
+    out[:, BB_INERTIA:BB_INERTIA + 9] = (I0 + Ip + mu[:, None, None] * pa).reshape(N, 9)
+    return out[0] if single else out
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -216,6 +324,7 @@ class Engine:
         self._stream = None  # the bound caller stream object (kept alive while bound)
         self._bound_tables = {}  # table name -> the bound device table's owner (kept alive while bound)
         self.params = WbcParams.from_buffer_copy(params) if params else default_params()  # the engine-wide wbc_params
+        self.model = WbcModel.from_buffer_copy(model) if model else anymal_model()  # the engine's model
         self.h = C.c_void_p()
         rc = self.lib.wbc_create(C.byref(model) if model else None, C.byref(params) if params else None,
                                  self.batch, int(device), C.byref(self.h))
@@ -314,6 +423,23 @@ class Engine:
     def contact_normals(self) -> np.ndarray:
         """wbc_get_contact_normals: the [B, 12] table in force (without one: (0, 0, 1) for every foot)."""
         return self._get_table("contact_normals")
+
+    def set_base_body(self, table):
+        """wbc_set_base_body: per-robot base body (mass, CoM, inertia: a payload on the trunk) for the
+        default step.  `table`: a (B, 14) array, one (14,) row, or a dict {mass, com, inertia} of one
+        value or per-robot arrays (base_body_table; rows for a payload: base_body_with_payload); None
+        clears the table: the model's base."""
+        self._set_table("base_body", None if table is None else base_body_table(self.batch, self.model, table))
+
+    def bind_device_base_body(self, table=0):
+        """wbc_bind_device_base_body: a caller-owned device table [B, 14] of doubles (no copy, no host
+        validation): an integer device pointer, or an object with data_ptr() (a torch tensor), which the
+        engine keeps referenced while it is bound.  0 / None: the engine-owned table, or none."""
+        self._bind_table("base_body", table)
+
+    def base_body(self) -> np.ndarray:
+        """wbc_get_base_body: the [B, 14] table in force (without one: the model's base in every row)."""
+        return self._get_table("base_body")
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

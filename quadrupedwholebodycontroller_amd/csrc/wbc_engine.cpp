@@ -24,14 +24,16 @@ extern "C" hipError_t wbc_launch_update(const wbc::KernelArgs* a, hipStream_t st
 extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st);
 // The default step's launchers (wbc_launch_update_solve_<unit> of wbc_kernel_<unit>.hip), indexed by
-// wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's
+// wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's; the base-body units'
+// (WBC_STEP_UNITS_BB) follow the nine
 #define X(unit) extern "C" hipError_t wbc_launch_update_solve_##unit(const wbc::KernelArgs* a, hipStream_t st);
 WBC_STEP_UNITS(X)
+WBC_STEP_UNITS_BB(X)
 #undef X
 #define X(unit) wbc_launch_update_solve_##unit,
-static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X)};
+static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X)};
 #undef X
-static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_INSTANCES, "one launcher per instance");
+static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_ALL_INSTANCES, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
@@ -91,6 +93,13 @@ struct wbc_engine {
     RobotTable rp{WBC_RP_LEN};
     RobotTable cn{WBC_CN_LEN};
     double* d_rp_uni = nullptr;
+    // per-robot base bodies (KernelArgs::bb, [B][WBC_BB_LEN]; without: the model's base).  The kernels
+    // that read them are contact-normal instances, so without normals in force their step reads
+    // d_cn_flat: (0, 0, 1) at every foot in B rows (built at the first use), and d_rp_uni as above.
+    // base_row: the model's own base as a row (what wbc_get_base_body returns without a table)
+    RobotTable bb{WBC_BB_LEN};
+    double* d_cn_flat = nullptr;
+    double base_row[WBC_BB_LEN] = {};
     // owned inputs: one device block [pose | nu | qj | ref | contacts | switching] (so a host cycle
     // is one H2D copy), and the outputs one block [tau | grf | status | iters | x] (wbc_layout.h
     // input_view / output_view: own_in, own_out)
@@ -176,8 +185,9 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    a.rp = h->rp.in_force ? h->rp.in_force : (h->cn.in_force ? h->d_rp_uni : nullptr);
-    a.cn = h->cn.in_force;
+    a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force) ? h->d_rp_uni : nullptr);
+    a.cn = h->cn.in_force ? h->cn.in_force : (h->bb.in_force ? h->d_cn_flat : nullptr);
+    a.bb = h->bb.in_force;
     a.base_pose = in.pose;
     a.nu = in.nu;
     a.qj = in.qj;
@@ -391,17 +401,21 @@ hipError_t launch_solves(wbc_engine* h, wbc::KernelArgs& a) {
 
 // The per-robot tables are read by the default wbc_step (and the plain wbc_cycle) only: with one in
 // force `call` is refused, outright (forms = 0) or when `flags` ask for one of `forms`.  The
-// parameter table is named before the normals; `allowed` says what the call may still do.
+// parameter table is named before the normals, the base bodies last; `allowed` says what the call may
+// still do.
 int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uint32_t forms, const char* allowed) {
     if (forms && !(flags & forms)) return WBC_OK;
     const char* form = !forms ? nullptr : (flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT";
-    for (const bool cn : {false, true}) {
-        if (!(cn ? h->cn : h->rp).in_force) continue;
-        const std::string what = cn ? "contact normals" : "a per-robot parameter table";
-        return fail(WBC_ERR_STATE, std::string(call) + ": " +
-                                       (form ? form + (" with " + what) + " in force" : what + (cn ? " are in force" : " is in force")) +
-                                       " (" + allowed + "; clear " + (cn ? "them with wbc_set_contact_normals" : "it with wbc_set_robot_params") +
-                                       "(h, NULL))");
+    static const struct { RobotTable wbc_engine::*table; const char *what, *is, *clear; } kTables[] = {
+        {&wbc_engine::rp, "a per-robot parameter table", " is in force", "it with wbc_set_robot_params"},
+        {&wbc_engine::cn, "contact normals", " are in force", "them with wbc_set_contact_normals"},
+        {&wbc_engine::bb, "a per-robot base body table", " is in force", "it with wbc_set_base_body"},
+    };
+    for (const auto& t : kTables) {
+        if (!(h->*t.table).in_force) continue;
+        const std::string what = t.what;
+        return fail(WBC_ERR_STATE, std::string(call) + ": " + (form ? form + (" with " + what) + " in force" : what + t.is) +
+                                       " (" + allowed + "; clear " + t.clear + "(h, NULL))");
     }
     return WBC_OK;
 }
@@ -504,6 +518,9 @@ int32_t wbc_create(const wbc_model* model, const wbc_params* params, int32_t bat
     hipStream_t st = h->stream;
     wbc::LdsImage limg;
     wbc::build_lds_image(m, p.friction, limg);
+    h->base_row[WBC_BB_MASS] = m.base_mass;
+    for (int i = 0; i < 3; ++i) h->base_row[WBC_BB_COM + i] = m.base_com[i];
+    for (int i = 0; i < 9; ++i) h->base_row[WBC_BB_INERTIA + i] = m.base_inertia[i];
     if (hipMemcpyAsync(h->d_model, &m, sizeof(m), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(h->d_params, &p, sizeof(p), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(h->d_limg, &limg, sizeof(limg), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -542,7 +559,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_box) (void)hipHostFree(h->res_box);
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
-                    h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni};
+                    h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -628,34 +645,44 @@ static void rp_engine_row(const wbc_params& p, double* row) {
     const double r[WBC_RP_LEN] = {p.friction, p.max_torque, p.kp, p.kp_z, p.kd, p.ki, p.kp_swing, p.kd_swing, p.slack_weight, 0.0};
     std::memcpy(row, r, sizeof(r));
 }
-// the uniform parameter table the contact-normal kernels read when no parameter table is in force
-static int32_t ensure_rp_uniform(wbc_engine* h) {
-    if (h->d_rp_uni) return WBC_OK;
+// an engine-owned device table of B equal rows (built once: *slot stays)
+static int32_t ensure_uniform(wbc_engine* h, double** slot, const double* row, size_t len, const char* what) {
+    if (*slot) return WBC_OK;
     const size_t B = (size_t)h->batch;
-    double row[WBC_RP_LEN];
-    rp_engine_row(h->params, row);
-    std::vector<double> t(B * WBC_RP_LEN);
-    for (size_t b = 0; b < B; ++b) std::memcpy(t.data() + b * WBC_RP_LEN, row, sizeof(row));
+    std::vector<double> t(B * len);
+    for (size_t b = 0; b < B; ++b) std::memcpy(t.data() + b * len, row, len * sizeof(double));
     WBC_HIP(hipSetDevice(h->device));
     double* d = nullptr;
-    if (dalloc(&d, B * WBC_RP_LEN) != hipSuccess) return fail(WBC_ERR_HIP, "hipMalloc failed: d_rp_uni");
+    if (dalloc(&d, B * len) != hipSuccess) return fail(WBC_ERR_HIP, std::string("hipMalloc failed: ") + what);
     const hipError_t e = hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(d);
-        return fail(WBC_ERR_HIP, std::string("hipMemcpy failed: d_rp_uni: ") + hipGetErrorString(e));
+        return fail(WBC_ERR_HIP, std::string("hipMemcpy failed: ") + what + ": " + hipGetErrorString(e));
     }
-    h->d_rp_uni = d;
+    *slot = d;
     return WBC_OK;
+}
+static const double kFlatNormals[WBC_CN_LEN] = {0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0};
+// the uniform parameter table the contact-normal kernels read when no parameter table is in force
+static int32_t ensure_rp_uniform(wbc_engine* h) {
+    double row[WBC_RP_LEN];
+    rp_engine_row(h->params, row);
+    return ensure_uniform(h, &h->d_rp_uni, row, WBC_RP_LEN, "d_rp_uni");
+}
+// and the flat normals the base-body kernels read when no normals are in force
+static int32_t ensure_rp_cn_uniform(wbc_engine* h) {
+    if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    return ensure_uniform(h, &h->d_cn_flat, kFlatNormals, WBC_CN_LEN, "d_cn_flat");
 }
 
 // The three calls of a per-robot table (RobotTable), for the parameters and for the normals.  What
 // differs is passed in: `call` (the C entry point, for messages), `what` (the own table's name in
-// allocation errors), row_error (why the host refuses row b, or "" for a row it accepts), uniform_rp
-// (the table's kernels read a parameter table too: ensure_rp_uniform) and, to read back without a
-// table in force, the default rows.
+// allocation errors), row_error (why the host refuses row b, or "" for a row it accepts), uniform
+// (the table's kernels read other tables too: ensure_rp_uniform, ensure_rp_cn_uniform; or null) and,
+// to read back without a table in force, the default rows.
 // Set from the host: a refused table leaves the previous one in force.
 static int32_t table_set(wbc_engine* h, RobotTable wbc_engine::*which, const double* table, const char* call,
-                         const char* what, std::string (*row_error)(const double* row), bool uniform_rp) {
+                         const char* what, std::string (*row_error)(const double* row), int32_t (*uniform)(wbc_engine*)) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     RobotTable& t = h->*which;
     if (!table) {  // back to no table of the engine's own (or to a caller's bound table)
@@ -669,8 +696,8 @@ static int32_t table_set(wbc_engine* h, RobotTable wbc_engine::*which, const dou
         if (!why.empty()) return fail(WBC_ERR_ARG, std::string(call) + ": row " + std::to_string(b) + ", " + why);
     }
     WBC_HIP(sync_own(h));
-    if (uniform_rp) {
-        if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    if (uniform) {
+        if (const int32_t rc = uniform(h)) return rc;
     }
     WBC_HIP(hipSetDevice(h->device));
     if (!t.own && dalloc(&t.own, B * t.row) != hipSuccess) return fail(WBC_ERR_HIP, std::string("hipMalloc failed: ") + what);
@@ -682,13 +709,13 @@ static int32_t table_set(wbc_engine* h, RobotTable wbc_engine::*which, const dou
 }
 // Bind a caller's device table (no copy, no host validation), or unbind it (null)
 static int32_t table_bind(wbc_engine* h, RobotTable wbc_engine::*which, const double* d_table, const char* call,
-                          bool uniform_rp) {
+                          int32_t (*uniform)(wbc_engine*)) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     RobotTable& t = h->*which;
     if (d_table && (reinterpret_cast<uintptr_t>(d_table) & 15u))
         return fail(WBC_ERR_ARG, std::string(call) + ": the table must be 16-byte aligned");
-    if (d_table && uniform_rp) {
-        if (const int32_t rc = ensure_rp_uniform(h)) return rc;
+    if (d_table && uniform) {
+        if (const int32_t rc = uniform(h)) return rc;
     }
     t.bound = d_table;
     t.in_force = d_table ? d_table : (t.has_own ? t.own : nullptr);
@@ -720,6 +747,16 @@ static std::string rp_row_error(const double* row) {
     return "column " + std::to_string(c) + " (" + names[c] + ") = " + val +
            ": need finite entries, friction >= 0, max_torque >= 0, slack_weight > 0";
 }
+static std::string bb_row_error(const double* row) {
+    static const char* const names[WBC_BB_LEN - 1] = {"mass", "com_x", "com_y", "com_z", "I_xx", "I_xy", "I_xz", "I_yx", "I_yy",
+                                                      "I_yz", "I_zx", "I_zy", "I_zz"};
+    const int c = wbc::bb_bad_entry(row);
+    if (c < 0) return "";
+    char val[32];
+    std::snprintf(val, sizeof(val), "%g", row[c]);
+    return "column " + std::to_string(c) + " (" + names[c] + ") = " + val +
+           ": need finite entries, mass > 0 and a symmetric (to 1e-9 of its trace), positive definite inertia";
+}
 static std::string cn_row_error(const double* row) {
     static const char* const feet[WBC_NUM_LEGS] = {"LH", "LF", "RF", "RH"};
     const int l = wbc::cn_bad_foot(row);
@@ -732,10 +769,10 @@ static std::string cn_row_error(const double* row) {
 }
 
 int32_t wbc_set_robot_params(wbc_engine* h, const double* table) {
-    return table_set(h, &wbc_engine::rp, table, "wbc_set_robot_params", "d_rp", rp_row_error, false);
+    return table_set(h, &wbc_engine::rp, table, "wbc_set_robot_params", "d_rp", rp_row_error, nullptr);
 }
 int32_t wbc_bind_device_robot_params(wbc_engine* h, const double* d_table) {
-    return table_bind(h, &wbc_engine::rp, d_table, "wbc_bind_device_robot_params", false);
+    return table_bind(h, &wbc_engine::rp, d_table, "wbc_bind_device_robot_params", nullptr);
 }
 int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
     if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
@@ -747,14 +784,26 @@ int32_t wbc_get_robot_params(wbc_engine* h, double* table) {
 }
 
 int32_t wbc_set_contact_normals(wbc_engine* h, const double* table) {
-    return table_set(h, &wbc_engine::cn, table, "wbc_set_contact_normals", "d_cn", cn_row_error, true);
+    return table_set(h, &wbc_engine::cn, table, "wbc_set_contact_normals", "d_cn", cn_row_error, ensure_rp_uniform);
 }
 int32_t wbc_bind_device_contact_normals(wbc_engine* h, const double* d_table) {
-    return table_bind(h, &wbc_engine::cn, d_table, "wbc_bind_device_contact_normals", true);
+    return table_bind(h, &wbc_engine::cn, d_table, "wbc_bind_device_contact_normals", ensure_rp_uniform);
 }
 int32_t wbc_get_contact_normals(wbc_engine* h, double* table) {
-    static const double flat[WBC_CN_LEN] = {0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0};
-    return table_get(h, &wbc_engine::cn, table, flat);
+    return table_get(h, &wbc_engine::cn, table, kFlatNormals);
+}
+
+int32_t wbc_set_base_body(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::bb, table, "wbc_set_base_body", "d_bb", bb_row_error, ensure_rp_cn_uniform);
+}
+int32_t wbc_bind_device_base_body(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::bb, d_table, "wbc_bind_device_base_body", ensure_rp_cn_uniform);
+}
+int32_t wbc_get_base_body(wbc_engine* h, double* table) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    if (const int32_t rc = table_get(h, &wbc_engine::bb, table, h->base_row)) return rc;
+    for (size_t b = 0; b < (size_t)h->batch; ++b) table[b * WBC_BB_LEN + WBC_BB_LEN - 1] = 0.0;  // the reserved column
+    return WBC_OK;
 }
 
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
@@ -820,9 +869,10 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         // host knows to be all 15 (no map then) runs the stance-only one, scheduled for it alone
         // (DESIGN.md 4.22), any other step the stateless or the stateful one; the same three under a
         // per-robot parameter table in force and under contact normals, which read the
-        // parameter table too (the caller's, or the engine's uniform one)
+        // parameter table too (the caller's, or the engine's uniform one), and under a
+        // base-body table, which reads normals and parameters too
         WBC_HIP(begin_step16(h, a, flags, io.qmap));
-        WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0)](&a, h->stream));
+        WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr)](&a, h->stream));
     }
     if (timed) {
         WBC_HIP(hipEventRecord(h->ev1, h->stream));

@@ -1,11 +1,11 @@
 // wbc_kernel.hip — batched whole-body-control step for gfx950 (MI355X), fp64.
 //
-// (Eleven translation units, wbc_kernel_<unit>.hip, include this file to build one kernel each under
-// its own schedule (Makefile KTU).  Nine hold one instance of the default
-// step each, wbc_update_solve_kernel<STF, SONLY, RP, CN>: stance, step0, step1 the plain ones
+// (Fourteen translation units, wbc_kernel_<unit>.hip, include this file to build one kernel each under
+// its own schedule (Makefile KTU).  Twelve hold one instance of the default
+// step each, wbc_update_solve_kernel<STF, SONLY, RP, CN, BB>: stance, step0, step1 the plain ones
 // (stance-only, stateless, stateful), rps, rp0, rp1 the same under a per-robot parameter table (15),
-// cns, cn0, cn1 under per-robot contact normals (16).  Such a unit names its launcher and its four
-// template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
+// cns, cn0, cn1 under per-robot contact normals (16), bbs, bb0, bb1 under a per-robot base body (18).
+// Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
 // unit builds the rest: the split and fused forms, the wave map's builder, the reset.)
@@ -2450,12 +2450,15 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false>
+          bool RP = false, bool CN = false, bool BB = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
-                             [[maybe_unused]] const double* cnf = nullptr) {
+                             [[maybe_unused]] const double* cnf = nullptr, [[maybe_unused]] const double* bbr = nullptr) {
     const wbc_params& pr = a.pv;
+    // BB (the base-body instances, KernelArgs::bb): bbr is the robot's base body, 13 doubles laid out as
+    // the model's first 13 (mass, com, inertia: a wbc.h WBC_BB_LEN row in LDS, or the model's own base
+    // for a row the step does not accept); it stands in for md's base at the four places that read it
     const bool switching = a.switching[rb] != 0;
     const bool stateful = STF < 0 ? a.stateful != 0 : STF == 1;  // (STF: as solve16's)
     const bool debug = a.debug != 0;
@@ -2679,6 +2682,9 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
                 const auto& lk = md.link[(lane - 1) / 3][(lane - 1) % 3];
                 mb = lk.mass; com = lk.com; Il = lk.inertia;
             }
+            if constexpr (BB) {
+                if (lane == 0) { mb = bbr[WBC_BB_MASS]; com = bbr + WBC_BB_COM; Il = bbr + WBC_BB_INERTIA; }
+            }
             double R[9], o[3], w[3], al[3], ao[3], vo[3], rel[3], t[3], u[3];
 #pragma unroll
             for (int i = 0; i < 9; ++i) R[i] = f.R[i];
@@ -2739,6 +2745,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         for (int r = 0; r < 3; ++r) s.Jf[l][3 * r + k] = col[r];
     }
     double m = md.base_mass;
+    if constexpr (BB) m = bbr[WBC_BB_MASS];
 #pragma unroll
     for (int l = 0; l < 4; ++l)
 #pragma unroll
@@ -2753,7 +2760,10 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
     {   // centroidal inertia: parallel-axis contributions of the 13 bodies, summed across lanes
         double t[6] = {0, 0, 0, 0, 0, 0};
         if (lane < 13) {
-            const double mb = (lane == 0) ? md.base_mass : md.link[(lane - 1) / 3][(lane - 1) % 3].mass;
+            double mb = (lane == 0) ? md.base_mass : md.link[(lane - 1) / 3][(lane - 1) % 3].mass;
+            if constexpr (BB) {
+                if (lane == 0) mb = bbr[WBC_BB_MASS];
+            }
             const Body& bd = s.bd[lane];
             double d[3] = {bd.c[0] - c[0], bd.c[1] - c[1], bd.c[2] - c[2]};
             const double dd = dot3(d, d);
@@ -3094,7 +3104,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         else mba = P.Ic[3 * (k - 3)] * ref[15] + P.Ic[3 * (k - 3) + 1] * ref[16] + P.Ic[3 * (k - 3) + 2] * ref[17];
         const double e = s.cen[CEN_POSE + k] - ref[k];
         P.W[k] = -kp * e - pr.kd * (s.cen[CEN_VC + k] - ref[6 + k]) - pr.ki * eint +
-                 (k == 2 ? md.total_mass * pr.gravity : 0.0) + mba;
+                 (k == 2 ? (BB ? md.total_mass + (bbr[WBC_BB_MASS] - md.base_mass) : md.total_mass) * pr.gravity : 0.0) + mba;
         if (stateful && wr) H[H_EINT + k] = eint + e * fast_rcp(pr.loop_rate);
     }
     // the default step's stateful instance only needs the LDS (P.Jbj) here: every read of the old
@@ -4758,9 +4768,14 @@ __device__ __forceinline__ int xcd_block(int b, int n) {
 // CN (with RP): the contact-normal instances (wbc_kernel_cn0.hip, wbc_kernel_cn1.hip,
 // wbc_kernel_cns.hip): each lane takes its own foot's ground normal (leg lane >> 2) from row qp of
 // KernelArgs::cn, indexed as the parameter row is, and builds its friction face from it.
-template <int STF, bool SONLY = false, bool RP = false, bool CN = false>
+// BB (with CN and RP): the base-body instances (wbc_kernel_bb0.hip, wbc_kernel_bb1.hip,
+// wbc_kernel_bbs.hip): lane k < 14 of a segment loads entry k of row qp of KernelArgs::bb, indexed as
+// the other rows are, into the segment's 14 doubles of LDS beside UpdLds (448 B per workgroup); the
+// update reads its base body there (update_phase's bbr).
+template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
+    static_assert(!BB || CN, "the base-body instances are contact-normal instances");
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
     const int K = a.modes;
@@ -4837,9 +4852,21 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) cnm[c] = m[c];
     }
+    // the QP's base-body row in the same batch: one entry per lane (lanes past the row reload its last)
+    [[maybe_unused]] double bbv = 0.0;
+    if constexpr (BB) bbv = a.bb[(size_t)qp * WBC_BB_LEN + (lane < WBC_BB_LEN ? lane : WBC_BB_LEN - 1)];
     // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy
     stage_to_lds<LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
     if (__all(empty)) return;  // the unused tail of a device-built map (uniform)
+    [[maybe_unused]] const double* bbr = nullptr;
+    if constexpr (BB) {
+        // the rows go to LDS before the staging barrier (their loads were issued before the image's, so
+        // they are back when it is), 4 x 14 doubles of the workgroup's own beside L
+        __shared__ double Lbb[UPD_RPW][WBC_BB_LEN];
+        static_assert(sizeof(UpdLds) + sizeof(Lbb) <= 40960, "four workgroups share a CU's LDS");
+        if (lane < WBC_BB_LEN) Lbb[seg][lane] = bbv;
+        bbr = &Lbb[seg][0];
+    }
     lds_sync();
     bool solved;
     if constexpr (RP) {
@@ -4862,8 +4889,21 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
             cn_frame(cnm, fn, ft1, ft2);
 #pragma unroll
             for (int r = 0; r < 3; ++r) cnf[r] = cn_face_elem(fn, ft1, ft2, ar.pv.friction, lane & 3, r);
-            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true>(
-                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf);
+            if constexpr (BB) {
+                // every lane checks its robot's whole row (LDS broadcast reads); a row the step does not
+                // accept flags the robot as above, and the update reads the model's own base meanwhile:
+                // LdsModel starts with the same 13 doubles (mass, com, inertia)
+                static_assert(offsetof(LdsModel, base_com) == WBC_BB_COM * sizeof(double) &&
+                              offsetof(LdsModel, base_inertia) == WBC_BB_INERTIA * sizeof(double), "LdsModel starts as a row does");
+                double bw[WBC_BB_LEN - 1];
+#pragma unroll
+                for (int c = 0; c < WBC_BB_LEN - 1; ++c) bw[c] = bbr[c];
+                const bool bbad = seg_any<UPD_SUB>(bb_bad_entry(bw) >= 0);
+                if (bbad) vin[0] = __builtin_nan("");
+                if (bbad) bbr = &L.model.base_mass;
+            }
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB>(
+                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr);
         } else
         solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true>(ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg],
                                                                                 nullptr, L.model, &L.fric[0], vin);
@@ -5315,9 +5355,9 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 }  // namespace wbc
 
 #ifdef WBC_STEP_INSTANCE
-// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN>, in a translation unit
+// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB]>, in a translation unit
 // of its own so that its schedule can be chosen apart from the other kernels' (Makefile <UNIT>_KFLAGS):
-// the unit file names the launcher and the four template arguments, the engine picks the launcher
+// the unit file names the launcher and the template arguments, the engine picks the launcher
 // (wbc_engine.cpp kStepLaunchers, wbc_layout.h step_instance).  The step in one launch: the update
 // kernel reducing and solving every QP inline, and the QPs whose reduction was not usable with the
 // general method in the same wave (drain_fallbacks: their records carry their own mask and bounds,

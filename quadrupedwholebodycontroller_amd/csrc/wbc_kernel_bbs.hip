@@ -1,0 +1,9 @@
+// wbc_kernel_bbs.hip — the stance-only default step under a per-robot base body
+// (wbc_update_solve_kernel<0, true, true, true, true>, KernelArgs::bb: wbc_set_base_body /
+// wbc_bind_device_base_body).  A contact-normal and per-robot-parameter instance too
+// (the engine feeds it flat normals and its uniform parameters when no such table is in force).  A
+// translation unit of its own (Makefile BBS_KFLAGS); the code is wbc_kernel.hip's, which
+// WBC_STEP_INSTANCE limits to this one kernel and its launcher.
+#define WBC_STEP_LAUNCHER wbc_launch_update_solve_bbs
+#define WBC_STEP_INSTANCE 0, true, true, true, true  // STF, SONLY, RP, CN, BB
+#include "wbc_kernel.hip"

@@ -198,6 +198,12 @@ struct KernelArgs {
     // engine points rp at a uniform table of its own when only normals are in force.  After rp, so
     // that no other argument's offset moves.
     const double* cn;
+    // Per-robot base body (wbc_set_base_body / wbc_bind_device_base_body): [batch][WBC_BB_LEN], row qp
+    // for QP qp (mass, CoM, inertia about the CoM; bb_bad_entry below); read only by the base-body
+    // instances of the default step (wbc_kernel_bb0.hip, wbc_kernel_bb1.hip, wbc_kernel_bbs.hip), which
+    // are contact-normal instances too: the engine points cn at a flat table of its own (and rp at its
+    // uniform one) when no such table is in force.  After cn, so that no other argument's offset moves.
+    const double* bb;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -226,15 +232,21 @@ WBC_HD inline int rp_bad_column(const double* r) {
 // instance or the reverse; mode hypotheses or a wave map for a stance-only instance (every QP mask
 // 15, in batch order); mode hypotheses or no table for a per-robot-parameter instance; no normals
 // for a contact-normal instance.
-inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a) {
+// BB (the base-body instances, a fifth template argument, false for the nine units above): no base-body
+// table.  The second form takes the flags in the template's order (a unit's WBC_STEP_INSTANCE).
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false) {
     if (a.nwaves <= 0 || (a.stateful != 0) != (STF != 0)) return true;
     if (SONLY && (a.modes || a.qmap)) return true;
     if (RP && (a.modes || !a.rp)) return true;
-    return CN && !a.cn;
+    if (CN && !a.cn) return true;
+    return BB && !a.bb;
+}
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, const KernelArgs& a) {
+    return step_args_refused(STF, SONLY, RP, CN, a, BB);
 }
 // The default step's instances, one kernel unit each (wbc_kernel_<unit>.hip): per table in force
-// (none, parameters, parameters + normals) the stateless instance of any mask mix, the stateful one,
-// the stance-only one.  The one list names the instances (STEP_<unit>) and, in the engine, orders the
+// (none, parameters, parameters + normals; parameters + normals + base bodies in the second list
+// below) the stateless instance of any mask mix, the stateful one, the stance-only one.  The one list names the instances (STEP_<unit>) and, in the engine, orders the
 // launcher table that StepInstance indexes (wbc_engine.cpp kStepLaunchers).  step_instance: the one
 // a step takes.  Normals come with a parameter table (the caller's or the engine's uniform one), so
 // cn wins over rp; all_stance (wbc_engine.cpp step_all_stance: stateless, every mask 15, no map, no
@@ -246,8 +258,21 @@ enum StepInstance {
 #undef X
     STEP_INSTANCES
 };
-constexpr StepInstance step_instance(bool cn, bool rp, bool all_stance, bool stateful) {
-    return all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
+// The base-body instances (KernelArgs::bb), in a list of their own whose values go on
+// from STEP_INSTANCES: the launcher table has STEP_ALL_INSTANCES entries, built from both lists
+// (DESIGN.md 17 says why there are two).  A base-body table comes with normals and parameters (the
+// caller's or the engine's), so bb wins over cn and rp.
+#define WBC_STEP_UNITS_BB(X) X(bb0) X(bb1) X(bbs)
+enum StepInstanceBB {
+    STEP_BB_FIRST_ = STEP_INSTANCES - 1,
+#define X(unit) STEP_##unit,
+    WBC_STEP_UNITS_BB(X)
+#undef X
+    STEP_ALL_INSTANCES
+};
+constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false) {
+    return bb ? (all_stance ? (int)STEP_bbs : stateful ? (int)STEP_bb1 : (int)STEP_bb0)
+         : all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
          : stateful   ? (cn ? STEP_cn1 : rp ? STEP_rp1 : STEP_step1)
                       : (cn ? STEP_cn0 : rp ? STEP_rp0 : STEP_step0);
 }
@@ -332,6 +357,26 @@ WBC_HD inline void cn_frame(const double* m, double* n, double* t1, double* t2) 
 WBC_HD inline double cn_face_elem(const double* n, const double* t1, const double* t2, double mu, int rr, int r) {
     const double t = (rr < 2) ? t1[r] : t2[r];
     return __builtin_fma(mu, n[r], (rr & 1) ? t : -t);
+}
+// A base-body row (wbc.h WBC_BB_*: mass, com[3], inertia[9] about the CoM in base axes, one reserved)
+// the step accepts: -1, or the first column that fails: every entry of columns 0-12 finite, mass > 0,
+// |I_ij - I_ji| <= 1e-9 trace (reported at the upper entry), the symmetric part positive definite
+// (leading minors > 0, reported at I_00, I_11, I_22).  The reserved column is not read.  One
+// definition for the host's validation (wbc_set_base_body) and the kernels' (a device-bound row).
+WBC_HD inline int bb_bad_entry(const double* r) {
+    for (int c = 0; c < WBC_BB_LEN - 1; ++c)
+        if (!__builtin_isfinite(r[c])) return c;
+    if (!(r[WBC_BB_MASS] > 0.0)) return WBC_BB_MASS;
+    const double* I = r + WBC_BB_INERTIA;
+    const double tol = 1e-9 * __builtin_fabs(I[0] + I[4] + I[8]);  // (a valid row has a positive trace)
+    if (!(__builtin_fabs(I[1] - I[3]) <= tol)) return WBC_BB_INERTIA + 1;
+    if (!(__builtin_fabs(I[2] - I[6]) <= tol)) return WBC_BB_INERTIA + 2;
+    if (!(__builtin_fabs(I[5] - I[7]) <= tol)) return WBC_BB_INERTIA + 5;
+    const double a = I[0], d = I[4], f = I[8], b = 0.5 * (I[1] + I[3]), c = 0.5 * (I[2] + I[6]), e = 0.5 * (I[5] + I[7]);
+    if (!(a > 0.0)) return WBC_BB_INERTIA;
+    if (!(a * d - b * b > 0.0)) return WBC_BB_INERTIA + 4;
+    if (!(a * (d * f - e * e) - b * (b * f - e * c) + c * (b * e - d * c) > 0.0)) return WBC_BB_INERTIA + 8;
+    return -1;
 }
 WBC_HD inline int32_t qmap_entry(int qp, int mask) { return (int32_t)((qp << 4) | (mask & 15)); }
 constexpr int QMAP_SEG = 4;  // QPs per wave (UPD_RPW of the kernel)
