@@ -196,11 +196,13 @@ def _givens(a, b):
     return a / r, b / r
 
 
-def gi_solve(H, g, CE, ce, CI, ci, max_iter=100):
+def gi_solve(H, g, CE, ce, CI, ci, max_iter=100, selnorm=None, tolv=None):
     """min 1/2 x'Hx + g'x  s.t. CE x = ce, CI x >= ci.  H symmetric positive definite.
 
     Returns (x, status, iters, active) with `iters` = inequality working-set changes (the
-    quantity qpOASES bounds by nWSR, cpp:517)."""
+    quantity qpOASES bounds by nWSR, cpp:517).  selnorm / tolv (default: each inequality's row norm
+    and 1e-10 max(1, |ci|)): its selection scale (slack / selnorm) and violation tolerance, as
+    oracle/wbc_ref.c gi_solve takes them for the 12-variable form."""
     n = g.size
     me, mi = CE.shape[0], CI.shape[0]
     try:
@@ -214,6 +216,8 @@ def gi_solve(H, g, CE, ce, CI, ci, max_iter=100):
     active = []  # constraint ids: ('e', i) or ('i', i)
     u = np.zeros(0)
     ni = np.linalg.norm(CI, axis=1) if mi else np.zeros(0)
+    if selnorm is not None:
+        ni = np.asarray(selnorm, float)
     eps = 1e-14
 
     def add(d):
@@ -277,7 +281,7 @@ def gi_solve(H, g, CE, ce, CI, ci, max_iter=100):
                 inact[i] = False
         s_all = CI @ x - ci
         viol = np.where(inact, s_all / np.maximum(ni, 1e-300), np.inf)
-        tol = 1e-10 * np.maximum(1.0, np.abs(ci)) / np.maximum(ni, 1e-300)
+        tol = (1e-10 * np.maximum(1.0, np.abs(ci)) if tolv is None else np.asarray(tolv, float)) / np.maximum(ni, 1e-300)
         cand = np.where(viol < -tol)[0]
         if cand.size == 0:
             return x, QP_OK, iters, active

@@ -674,6 +674,31 @@ int wbc_ref_gi(int n, const double* H, const double* g, int me, const double* CE
     return gi_solve(n, H, g, me, CE, ce, mi, CI, ci, max_iter, NULL, 0, x, iters, NULL, NULL, NULL, NULL, 0);
 }
 
+/* ------------------------------------------------------------------ sloped ground */
+/* The four friction faces D (4 x 3, D[rr] f <= 0) of a foot whose ground normal is m (world frame),
+ * by the rule of tests/contact_normals_oracle.py `frame` / `faces`: n = m / |m|, t1 = e_x less its
+ * part along n, normalised, t2 = n x t1; faces t1 - mu n, -(t1 + mu n), t2 - mu n, -(t2 + mu n), the
+ * order of computeNonSlidingConstraints (cpp:404-424).  Used only when a call passes normals
+ * (wbc_ref_step_normals): without them both friction sites keep their flat-ground table. */
+static void friction_faces(const double* m, double mu, double* D) {
+    const double s = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+    const double n[3] = {m[0] / s, m[1] / s, m[2] / s};
+    const double u[3] = {1.0 - n[0] * n[0], 0.0 - n[0] * n[1], 0.0 - n[0] * n[2]};
+    const double us = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    const double t1[3] = {u[0] * us, u[1] * us, u[2] * us};
+    double t2[3];
+    cross(n, t1, t2);
+    for (int c = 0; c < 3; ++c) {
+        D[0 + c] = t1[c] - mu * n[c];
+        D[3 + c] = -(t1[c] + mu * n[c]);
+        D[6 + c] = t2[c] - mu * n[c];
+        D[9 + c] = -(t2[c] + mu * n[c]);
+    }
+}
+static void all_faces(const double* normals, double mu, double (*Dn)[12]) {
+    for (int l = 0; l < NL; ++l) friction_faces(normals + 3 * l, mu, Dn[l]);
+}
+
 /* ------------------------------------------------------------------ the engine's 12-variable form */
 /* The same QP reduced exactly to 12 variables for every contact mask (the numpy
  * restatement oracle/wbc_reduced.py documents the derivation): z = one 3-slot per leg (a swing
@@ -689,7 +714,7 @@ int wbc_ref_gi(int n, const double* H, const double* g, int me, const double* CE
 static int reduced_solve(const wbc_params* pr, wbc_ref_state* st, const wbc_ref_kindyn_t* kd, const double* T,
                          const double* Tinv, const double* Mbar_b, const double* Mbar_j, const double* bbar,
                          const double* W, const double* r1, const double* rsw, const int* kap, double* x, double* tau,
-                         int* iters) {
+                         int* iters, const double* normals) {
     double Jbar[12 * ND], E[12 * 6], Jbj[144], K[6 * 12], Jl[4][9];
     mat_mul(kd->foot_J, Tinv, Jbar, 12, ND, ND);
     for (int i = 0; i < 12; ++i) {
@@ -857,12 +882,15 @@ static int reduced_solve(const wbc_params* pr, wbc_ref_state* st, const wbc_ref_
     const double D[12] = {1, 0, -mu, -1, 0, -mu, 0, 1, -mu, 0, -1, -mu};
     double CI[40 * 12], ci[40], seln[40], tolv[40];
     int ids[40], mi = 0, idpos[40];
+    double Dn[NL][12];
+    if (normals) all_faces(normals, mu, Dn);
     for (int t = 0; t < 40; ++t) idpos[t] = -1;
     for (int l = 0; l < 4; ++l) {
         if (!kap[l]) continue;
+        const double* Dl = normals ? Dn[l] : D;
         for (int rr = 0; rr < 4; ++rr) {
             for (int j = 0; j < 12; ++j) CI[mi * 12 + j] = 0.0;
-            for (int c = 0; c < 3; ++c) CI[mi * 12 + 3 * l + c] = -D[rr * 3 + c];
+            for (int c = 0; c < 3; ++c) CI[mi * 12 + 3 * l + c] = -Dl[rr * 3 + c];
             ci[mi] = 0.0;
             seln[mi] = sqrt(1.0 + mu * mu);
             tolv[mi] = 1e-10;
@@ -955,9 +983,9 @@ void wbc_ref_state_init(wbc_ref_state* s) { /* setInitialState, cpp:65-120 (hist
     s->contacts = 15;
 }
 
-int wbc_ref_step(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, const double* pose, const double* nu,
-                 const double* qj, const double* ref, int contacts, int switching, double* tau, double* grf, double* x,
-                 int* iters, wbc_ref_debug_t* dbg) {
+static int step_impl(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, const double* pose, const double* nu,
+                     const double* qj, const double* ref, int contacts, int switching, double* tau, double* grf, double* x,
+                     int* iters, wbc_ref_debug_t* dbg, const double* normals) {
     wbc_ref_kindyn_t kd;
     wbc_ref_kindyn(md, pose, nu, qj, &kd);
     const double* pB = pose;
@@ -1091,9 +1119,13 @@ int wbc_ref_step(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, c
         for (int i = 0; i < 3 * NL; ++i) { /* R1 */
             for (int j = 0; j < ND; ++j) A[(6 + i) * NV + j] = Jc[i * ND + j];
         }
-        for (int l = 0; l < NL; ++l) /* R2 */
+        double Dn[NL][12];
+        if (normals) all_faces(normals, mu, Dn);
+        for (int l = 0; l < NL; ++l) { /* R2 */
+            const double* Dl = normals ? Dn[l] : D;
             for (int rr = 0; rr < 4; ++rr)
-                for (int c = 0; c < 3; ++c) A[(18 + 4 * l + rr) * NV + 18 + 3 * l + c] = D[rr * 3 + c] * kap[l];
+                for (int c = 0; c < 3; ++c) A[(18 + 4 * l + rr) * NV + 18 + 3 * l + c] = Dl[rr * 3 + c] * kap[l];
+        }
         for (int i = 0; i < NJ; ++i) { /* R3 */
             for (int j = 0; j < NJ; ++j) A[(34 + i) * NV + 6 + j] = Mbar_j[i * NJ + j];
             for (int j = 0; j < 3 * NL; ++j) A[(34 + i) * NV + 18 + j] = -Jc[j * ND + 6 + i];
@@ -1133,7 +1165,7 @@ int wbc_ref_step(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, c
         double Tinv_r[ND * ND], rsw[12];
         for (int i = 0; i < 12; ++i) rsw[i] = ub[46 + i];
         if (mat_inv(T, Tinv_r, ND) == 0)
-            status = reduced_solve(pr, st, &kd, T, Tinv_r, Mbar_b, Mbar_j, bbar, W, lb + 6, rsw, kap, x, tau, &it);
+            status = reduced_solve(pr, st, &kd, T, Tinv_r, Mbar_b, Mbar_j, bbar, W, lb + 6, rsw, kap, x, tau, &it, normals);
         if (status < 0) st->ws12_valid = 0;
         else {
             *iters = it;
@@ -1194,6 +1226,17 @@ debug_out:
     return status;
 }
 
+int wbc_ref_step(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, const double* pose, const double* nu,
+                 const double* qj, const double* ref, int contacts, int switching, double* tau, double* grf, double* x,
+                 int* iters, wbc_ref_debug_t* dbg) {
+    return step_impl(md, pr, st, pose, nu, qj, ref, contacts, switching, tau, grf, x, iters, dbg, NULL);
+}
+int wbc_ref_step_normals(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, const double* pose, const double* nu,
+                         const double* qj, const double* ref, int contacts, int switching, double* tau, double* grf,
+                         double* x, int* iters, wbc_ref_debug_t* dbg, const double* normals) {
+    return step_impl(md, pr, st, pose, nu, qj, ref, contacts, switching, tau, grf, x, iters, dbg, normals);
+}
+
 void wbc_ref_run_batch(const wbc_model* md, const wbc_params* pr, int B, const double* pose, const double* nu,
                        const double* qj, const double* ref, const uint8_t* contacts, const uint8_t* switching, double* tau,
                        double* grf, double* x, int32_t* status, int32_t* iters) {
@@ -1214,6 +1257,21 @@ void wbc_ref_run_batch_method(const wbc_model* md, const wbc_params* pr, int B, 
     }
 }
 
+void wbc_ref_run_batch_normals(const wbc_model* md, const wbc_params* pr, int B, const double* pose, const double* nu,
+                               const double* qj, const double* ref, const uint8_t* contacts, const uint8_t* switching,
+                               double* tau, double* grf, double* x, int32_t* status, int32_t* iters, int method,
+                               const double* normals) {
+    for (int b = 0; b < B; ++b) {
+        wbc_ref_state st;
+        wbc_ref_state_init(&st);
+        st.method = method;
+        int it = 0;
+        status[b] = step_impl(md, pr, &st, pose + 7 * b, nu + 18 * b, qj + 12 * b, ref + 54 * b, contacts[b], switching[b],
+                              tau + 12 * b, grf + 12 * b, x + NV * b, &it, NULL, normals ? normals + 12 * b : NULL);
+        iters[b] = it;
+    }
+}
+
 /* n stateful robots stepped together (the per-robot `Robot` of oracle/wbc_ref.py, one call per
  * cycle): robot i reads row idx[i] of the batch input arrays and writes row i of the outputs.
  * The tests use it to follow a sample of a large batch through a whole trajectory. */
@@ -1227,6 +1285,20 @@ void wbc_ref_step_states(const wbc_model* md, const wbc_params* pr, int n, wbc_r
         int it = 0;
         status[i] = wbc_ref_step(md, pr, st + i, pose + 7 * b, nu + 18 * b, qj + 12 * b, ref + 54 * b, contacts[b],
                                  switching[b], tau + 12 * i, grf + 12 * i, x + NV * i, &it, NULL);
+        iters[i] = it;
+    }
+}
+
+void wbc_ref_step_states_normals(const wbc_model* md, const wbc_params* pr, int n, wbc_ref_state* st, const int32_t* idx,
+                                 const double* pose, const double* nu, const double* qj, const double* ref,
+                                 const uint8_t* contacts, const uint8_t* switching, double* tau, double* grf, double* x,
+                                 int32_t* status, int32_t* iters, int threads, const double* normals) {
+#pragma omp parallel for schedule(dynamic, 4) num_threads(threads > 0 ? threads : 1)
+    for (int i = 0; i < n; ++i) {
+        const int b = idx[i];
+        int it = 0;
+        status[i] = step_impl(md, pr, st + i, pose + 7 * b, nu + 18 * b, qj + 12 * b, ref + 54 * b, contacts[b], switching[b],
+                              tau + 12 * i, grf + 12 * i, x + NV * i, &it, NULL, normals ? normals + 12 * i : NULL);
         iters[i] = it;
     }
 }

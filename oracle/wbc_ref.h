@@ -44,6 +44,23 @@ void wbc_ref_run_batch(const wbc_model* md, const wbc_params* pr, int B, const d
 void wbc_ref_run_batch_method(const wbc_model* md, const wbc_params* pr, int B, const double* pose, const double* nu,
                               const double* qj, const double* ref, const uint8_t* contacts, const uint8_t* switching,
                               double* tau, double* grf, double* x, int32_t* status, int32_t* iters, int method);
+/* Sloped ground: the entry points above with per-foot ground normals, given per robot and per call and
+ * kept nowhere (wbc_ref_state is as it was, so a caller built against the earlier header still fits).
+ * normals: [4][3] of one robot (world frame, any length > 0): the friction faces of foot l stand on the
+ * frame of normals[l]; NULL: the stock flat-ground rows, the code of the entry point without normals. */
+int wbc_ref_step_normals(const wbc_model* md, const wbc_params* pr, wbc_ref_state* st, const double* pose, const double* nu,
+                         const double* qj, const double* ref, int contacts, int switching, double* tau, double* grf,
+                         double* x, int* iters, wbc_ref_debug_t* dbg, const double* normals);
+/* robot i (state st[i]) on normals + 12 i ([n][4][3], indexed as the outputs are) */
+void wbc_ref_step_states_normals(const wbc_model* md, const wbc_params* pr, int n, wbc_ref_state* st, const int32_t* idx,
+                                 const double* pose, const double* nu, const double* qj, const double* ref,
+                                 const uint8_t* contacts, const uint8_t* switching, double* tau, double* grf, double* x,
+                                 int32_t* status, int32_t* iters, int threads, const double* normals);
+/* wbc_ref_run_batch_method with robot b on normals + 12 b ([B][4][3]; NULL: wbc_ref_run_batch_method) */
+void wbc_ref_run_batch_normals(const wbc_model* md, const wbc_params* pr, int B, const double* pose, const double* nu,
+                               const double* qj, const double* ref, const uint8_t* contacts, const uint8_t* switching,
+                               double* tau, double* grf, double* x, int32_t* status, int32_t* iters, int method,
+                               const double* normals);
 /* n stateful robots in one call: robot i (state st[i]) reads batch row idx[i], writes output row i */
 void wbc_ref_step_states(const wbc_model* md, const wbc_params* pr, int n, wbc_ref_state* st, const int32_t* idx,
                          const double* pose, const double* nu, const double* qj, const double* ref,

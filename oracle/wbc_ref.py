@@ -57,6 +57,10 @@ def lib():
         _lib.wbc_ref_run_batch.argtypes = [P, P, C.c_int, P, P, P, P, P, P, P, P, P, P, P]
         _lib.wbc_ref_run_batch_method.argtypes = [P, P, C.c_int, P, P, P, P, P, P, P, P, P, P, P, C.c_int]
         _lib.wbc_ref_step_states.argtypes = [P, P, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, C.c_int]
+        _lib.wbc_ref_step_normals.argtypes = _lib.wbc_ref_step.argtypes + [P]
+        _lib.wbc_ref_step_normals.restype = C.c_int
+        _lib.wbc_ref_step_states_normals.argtypes = _lib.wbc_ref_step_states.argtypes + [P]
+        _lib.wbc_ref_run_batch_normals.argtypes = [P, P, C.c_int, P, P, P, P, P, P, P, P, P, P, P, C.c_int, P]
         _bind_baseline(_lib)
     return _lib
 
@@ -163,10 +167,20 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def run_batch(inp, method=LITERAL, **overrides):
+def step_call(normals):
+    """(function, trailing arguments) of one robot's step: wbc_ref_step itself without normals, else
+    wbc_ref_step_normals with the [4, 3] ground normals."""
+    if normals is None:
+        return lib().wbc_ref_step, ()
+    n = np.ascontiguousarray(normals, np.float64).reshape(12)
+    return lib().wbc_ref_step_normals, (_p(n),)
+
+
+def run_batch(inp, method=LITERAL, normals=None, **overrides):
     """Cold batch (every robot from setInitialState with the given switching flags).  Keyword
     arguments override wbc_params fields (e.g. max_torque=6.0, max_wsr=2).  method: LITERAL (the
-    42 x 70 QP as assembled at cpp:466-515) or REDUCED (the engine's 12-variable form)."""
+    42 x 70 QP as assembled at cpp:466-515) or REDUCED (the engine's 12-variable form).  normals:
+    [B, 4, 3] ground normals per robot and foot (tests/contact_normals_oracle.py's rule), or None."""
     m, p = model_params()
     if overrides:
         p2 = type(p)()
@@ -180,9 +194,14 @@ def run_batch(inp, method=LITERAL, **overrides):
     con, sw = f("contacts", np.uint8), f("switching", np.uint8)
     out = dict(tau=np.zeros((B, 12)), grf=np.zeros((B, 12)), x=np.zeros((B, 42)), status=np.zeros(B, np.int32),
                iters=np.zeros(B, np.int32))
-    lib().wbc_ref_run_batch_method(C.byref(m), C.byref(p), B, _p(pose), _p(nu), _p(qj), _p(ref), _p(con), _p(sw),
-                                   _p(out["tau"]), _p(out["grf"]), _p(out["x"]), _p(out["status"]), _p(out["iters"]),
-                                   int(method))
+    args = (C.byref(m), C.byref(p), B, _p(pose), _p(nu), _p(qj), _p(ref), _p(con), _p(sw), _p(out["tau"]), _p(out["grf"]),
+            _p(out["x"]), _p(out["status"]), _p(out["iters"]), int(method))
+    if normals is None:
+        lib().wbc_ref_run_batch_method(*args)
+    else:
+        nrm = np.ascontiguousarray(normals, np.float64)
+        assert nrm.shape == (B, 4, 3), nrm.shape
+        lib().wbc_ref_run_batch_normals(*args, _p(nrm))
     return out
 
 
@@ -199,7 +218,8 @@ class Robot:
         self.st.method = int(method)
         self.overrides = overrides
 
-    def step(self, pose, nu, qj, ref, contacts, switching, debug=False):
+    def step(self, pose, nu, qj, ref, contacts, switching, debug=False, normals=None):
+        """normals: this call's [4, 3] ground normals (None: flat ground, the stock rows)."""
         m, p = model_params()
         if self.overrides:
             p2 = type(p)()
@@ -211,9 +231,9 @@ class Robot:
         it = C.c_int()
         dbg = Debug() if debug else None
         a = [np.ascontiguousarray(v, np.float64) for v in (pose, nu, qj, ref)]
-        st = lib().wbc_ref_step(C.byref(m), C.byref(p), C.byref(self.st), *[_p(v) for v in a], int(contacts),
-                                int(switching), _p(tau), _p(grf), _p(x), C.byref(it),
-                                C.byref(dbg) if debug else None)
+        fn, extra = step_call(normals)
+        st = fn(C.byref(m), C.byref(p), C.byref(self.st), *[_p(v) for v in a], int(contacts), int(switching), _p(tau),
+                _p(grf), _p(x), C.byref(it), C.byref(dbg) if debug else None, *extra)
         out = dict(tau=tau, grf=grf, x=x, status=st, iters=it.value)
         if debug:
             out["dbg"] = {k: np.array(getattr(dbg, k)) for k, _ in Debug._fields_}
@@ -224,8 +244,11 @@ class Robots:
     """n stateful robots (each a `Robot`) stepped in one C call: robot i follows row idx[i] of the
     batch inputs passed to step() (a sample of a large batch followed through a trajectory)."""
 
-    def __init__(self, idx, hotstart=True, method=LITERAL, threads=8, **overrides):
+    def __init__(self, idx, hotstart=True, method=LITERAL, threads=8, normals=None, **overrides):
+        """normals: [n, 4, 3] ground normals, robot i on normals[i] (None: flat ground); the attribute
+        may be replaced between steps."""
         self.idx = np.ascontiguousarray(idx, np.int32)
+        self.normals = normals
         n = len(self.idx)
         self.st = (State * n)()
         for i in range(n):
@@ -257,7 +280,11 @@ class Robots:
         assert int(self.idx.max()) < len(con)
         out = dict(tau=np.zeros((n, 12)), grf=np.zeros((n, 12)), x=np.zeros((n, 42)), status=np.zeros(n, np.int32),
                    iters=np.zeros(n, np.int32))
-        lib().wbc_ref_step_states(C.byref(self.m), C.byref(self.p), n, self.st, _p(self.idx), _p(pose), _p(nu), _p(qj),
-                                  _p(ref), _p(con), _p(sw), _p(out["tau"]), _p(out["grf"]), _p(out["x"]),
-                                  _p(out["status"]), _p(out["iters"]), int(self.threads))
+        args = (C.byref(self.m), C.byref(self.p), n, self.st, _p(self.idx), _p(pose), _p(nu), _p(qj), _p(ref), _p(con), _p(sw),
+                _p(out["tau"]), _p(out["grf"]), _p(out["x"]), _p(out["status"]), _p(out["iters"]), int(self.threads))
+        if self.normals is None:
+            lib().wbc_ref_step_states(*args)
+        else:
+            nrm = np.ascontiguousarray(self.normals, np.float64).reshape(n, 12)
+            lib().wbc_ref_step_states_normals(*args, _p(nrm))
         return out

@@ -87,23 +87,30 @@ def c_run_batch(inp, rows, method=R.LITERAL, params_rows=None):
 
 
 class CRobot(R.Robot):
-    """wbc_ref.Robot (stateful) whose model may be replaced between steps: `row` is its base body."""
+    """wbc_ref.Robot (stateful) whose model may be replaced between steps: `row` is its base body.
+    overrides: wbc_params fields, as wbc_ref.Robot's (a row of the per-robot parameter table)."""
 
-    def __init__(self, row, hotstart=True, method=R.LITERAL):
-        super().__init__(hotstart, method)
+    def __init__(self, row, hotstart=True, method=R.LITERAL, **overrides):
+        super().__init__(hotstart, method, **overrides)
         self.model = c_model(row)
 
     def set_row(self, row):
         self.model = c_model(row)
 
-    def step(self, pose, nu, qj, ref, contacts, switching):
-        p = R.model_params()[1]
+    def step(self, pose, nu, qj, ref, contacts, switching, debug=False, normals=None):
+        """normals: this call's [4, 3] ground normals (None: flat ground); debug: the record under "dbg"."""
+        p = c_params(**self.overrides) if self.overrides else R.model_params()[1]
         tau, grf, x = np.zeros(12), np.zeros(12), np.zeros(42)
         it = C.c_int()
+        dbg = R.Debug() if debug else None
         a = [np.ascontiguousarray(v, np.float64) for v in (pose, nu, qj, ref)]
-        st = R.lib().wbc_ref_step(C.byref(self.model), C.byref(p), C.byref(self.st), *[R._p(v) for v in a], int(contacts),
-                                  int(switching), R._p(tau), R._p(grf), R._p(x), C.byref(it), None)
-        return dict(tau=tau, grf=grf, x=x, status=st, iters=it.value)
+        fn, extra = R.step_call(normals)
+        st = fn(C.byref(self.model), C.byref(p), C.byref(self.st), *[R._p(v) for v in a], int(contacts), int(switching),
+                R._p(tau), R._p(grf), R._p(x), C.byref(it), C.byref(dbg) if debug else None, *extra)
+        out = dict(tau=tau, grf=grf, x=x, status=st, iters=it.value)
+        if debug:
+            out["dbg"] = {k: np.array(getattr(dbg, k)) for k, _ in R.Debug._fields_}
+        return out
 
 
 def np_controller(inp, b, row, params=None, cls=W.ReferenceWBC, **kw):

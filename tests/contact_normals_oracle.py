@@ -1,5 +1,5 @@
 """The oracle of the per-robot contact normals (wbc_set_contact_normals, include/wbc.h),
-built on the numpy oracle without touching it: a subclass of wbc_np.ReferenceWBC whose friction rows
+built on the numpy oracle without changing what it computes: a subclass of wbc_np.ReferenceWBC whose friction rows
 stand on each foot's own frame, the same edit on the reduced 12-variable problem of
 wbc_reduced.reduced_problem, and the generator of the normal tables the tests use.
 
@@ -79,7 +79,10 @@ def sloped_reduced_problem(c):
 
 
 def reduced_step(c):
-    """wbc_reduced.reduced_step on the edited problem: (tau, x42, status, iters), or None (no reduction)."""
+    """wbc_reduced.reduced_step on the edited problem: (tau, x42, status, iters), or None (no reduction).
+    Rows are selected as the engine and the C oracle's REDUCED form select them, by slack over the norm
+    of the reference's row (the problem's `nsel`) with the reference row's tolerance, so `iters` counts
+    the same working-set walk as theirs."""
     c.update_state()
     c.assemble_qp()
     rp = sloped_reduced_problem(c)
@@ -87,7 +90,10 @@ def reduced_step(c):
         return None
     if not rp["vac_ok"]:
         return np.zeros(NJ), np.zeros(NV), W.QP_INFEASIBLE, 0
-    z, stt, it, _ = W.gi_solve(rp["H"], rp["g"], np.zeros((0, 12)), np.zeros(0), rp["CI"], rp["ci"], c.params["max_wsr"])
+    tm, bbj = c.params["max_torque"], c.bbar[6:]
+    tolv = [1e-10 if pid < 16 else 1e-10 * max(1.0, abs(-tm - (-1.0 if pid & 1 else 1.0) * bbj[(pid - 16) // 2])) for pid in rp["ids"]]
+    z, stt, it, _ = W.gi_solve(rp["H"], rp["g"], np.zeros((0, 12)), np.zeros(0), rp["CI"], rp["ci"], c.params["max_wsr"],
+                               selnorm=np.sqrt(np.maximum(rp["nsel"], 1e-300)), tolv=tolv)
     if stt != W.QP_OK:
         return np.zeros(NJ), np.zeros(NV), stt, it
     x, tau = WR.to_x42(c, rp, z)

@@ -139,3 +139,111 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
         if "drain_fallbacks" not in n:
             body = lines[i:min(x for x in ends if x > i)]
             assert not [l for l in body if "scratch_" in l], n
+
+
+# ---------------------------------------------------------------------------------------------------
+# The C oracle's per-foot normals (oracle/wbc_ref.c friction_faces, wbc_ref_state::normals): the fast
+# stateful checker of the cn1 / bb1 kernel instances (tests/test_gpu_stateful_offtrot.py), pinned here
+# by the numpy oracle above.
+import margins as M  # noqa: E402
+import stateful_sequences as S  # noqa: E402
+import wbc_ref as R  # noqa: E402
+
+SEQ = dict(B=8, dwell=3, seed=5)
+IN_KEYS = ("base_pose", "nu", "qj", "ref")
+
+
+def _c_sequence(latch, method, nrm):
+    robots = R.Robots(np.arange(SEQ["B"]), method=method, normals=nrm)
+    out = [robots.step(s) for s in S.sequence(SEQ["B"], SEQ["dwell"], SEQ["seed"], latch)]
+    return {k: np.array([o[k] for o in out]) for k in KEYS}
+
+
+@pytest.mark.parametrize("method", [R.LITERAL, R.REDUCED], ids=["literal", "reduced"])
+def test_c_flat_normals_are_the_c_oracle_without(method):
+    """Normals (0, 0, 1) on every foot against no normals at all (the stock code path, which the new
+    argument leaves alone): tau, x, grf, status and iters equal element for element, cold on
+    rl_random(61) and over the latched off-trot sequence with its hotstarts (6 144 robot-cycles)."""
+    inp = workloads.rl_random(61, seed=11)
+    a, b = R.run_batch(inp, method=method), R.run_batch(inp, method=method, normals=np.tile(CN.FLAT, (61, 1, 1)))
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), ("cold", k)
+    a, b = _c_sequence(True, method, None), _c_sequence(True, method, np.tile(CN.FLAT, (SEQ["B"], 1, 1)))
+    assert np.sum(a["status"] == W.QP_OK) >= 0.9 * a["status"].size
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), ("sequence", k)
+
+
+@pytest.mark.parametrize("name,B", [("rl_random", 61), ("stance_cold", 64)])
+def test_c_sloped_cold_against_numpy(name, B):
+    """Cold, feet tilted by up to 0.35 rad: C LITERAL against the numpy literal QP on the same frames, C
+    REDUCED against the numpy reduced problem with its friction rows edited (iters equal: the same
+    12-variable working-set walk), at the bounds of tests/test_oracle_reduced.py (x 1e-9, tau 1e-8 of
+    1 + max|.|); and the slopes move the C oracle's torques as they move the numpy oracle's."""
+    inp = getattr(workloads, name)(B, seed=11)
+    nrm = CN.normals(B, 5, 0.35)
+    lit, red = R.run_batch(inp, normals=nrm), R.run_batch(inp, method=R.REDUCED, normals=nrm)
+    ref = CN.run_batch(inp, nrm)
+    assert np.array_equal(lit["status"], ref["status"]) and np.array_equal(red["status"], ref["status"])
+    assert np.all(ref["status"] == W.QP_OK), ref["status"]
+    assert (np.abs(lit["tau"] - R.run_batch(inp)["tau"]).max(axis=1) > 1e-6).sum() >= B // 2
+    worst = dict(tau=0.0, x=0.0, rtau=0.0, rx=0.0)
+    for b in range(B):
+        worst["tau"] = max(worst["tau"], M.norm_err(lit["tau"][b], ref["tau"][b]))
+        worst["x"] = max(worst["x"], M.norm_err(lit["x"][b], ref["x"][b]))
+        assert np.array_equal(lit["grf"][b], lit["x"][b, 18:30])
+        r = CN.reduced_step(CN.controller(inp, b, nrm[b]))
+        assert r is not None and r[2] == red["status"][b], b
+        assert r[3] == red["iters"][b], (b, r[3], red["iters"][b])
+        worst["rtau"] = max(worst["rtau"], M.norm_err(red["tau"][b], r[0]))
+        worst["rx"] = max(worst["rx"], M.norm_err(red["x"][b], r[1]))
+    print(name, worst)
+    assert worst["tau"] <= 1e-8 and worst["rtau"] <= 1e-8 and worst["x"] <= 1e-9 and worst["rx"] <= 1e-9, worst
+
+
+@pytest.mark.parametrize("latch", [True, False], ids=["latched", "unlatched"])
+def test_c_sloped_stateful_against_numpy(latch):
+    """Robots 0 and 1 over the first 240 cycles (80 dwells) of the off-trot sequence under rows 0 and 1
+    of normals(8, 5, 0.35): the stateful C LITERAL robot against a stateful SlopedWBC.  Status equal, tau
+    within margins.TAU, bbar[6:], W, r1 and rsw within margins.STATEFUL_INTERMEDIATE, as
+    tests/test_stateful_sequences_cpu.py::test_numpy_and_c_oracle_agree_on_stateful_intermediates does on
+    flat ground.  Latched every solve is OK; unlatched both statuses occur (134 OK, 46 INFEASIBLE on the
+    first 90 cycles)."""
+    n, nrm = 240, CN.normals(SEQ["B"], 5, 0.35)
+    model, params = W.Model(), W.default_params()
+    n_ok = n_inf = 0
+    for b in (0, 1):
+        c_robot, np_robot = R.Robot(), CN.SlopedWBC(model, params, nrm[b])
+        for k, s in enumerate(S.sequence(SEQ["B"], SEQ["dwell"], SEQ["seed"], latch)[:n]):
+            con, sw = int(s["contacts"][b]), int(s["switching"][b])
+            c = c_robot.step(*[s[q][b] for q in IN_KEYS], con, sw, debug=True, normals=nrm[b])
+            CN.load(np_robot, s, b)
+            np_robot.step()
+            d, ref = c["dbg"], np_robot.debug_record()
+            assert c["status"] == np_robot.qp_status, (latch, b, k)
+            for q in ("bbar", "W", "r1", "rsw"):
+                x, y = (d[q][6:], ref[q][6:]) if q == "bbar" else (d[q], ref[q])
+                tol = M.STATEFUL_INTERMEDIATE[q]
+                err = float(np.max(np.abs(x - y) / np.maximum(1.0, np.abs(y))))
+                assert M.record(f"oracle spread {q}, sloped", err, tol) <= tol, (latch, b, k, q)
+            if c["status"] == W.QP_OK:
+                n_ok += 1
+                err = float(np.max(np.abs(c["tau"] - np_robot.tau) / np.maximum(1.0, np.abs(np_robot.tau))))
+                assert M.record("oracle spread tau, sloped", err, M.TAU) <= M.TAU, (latch, b, k)
+            else:
+                n_inf += c["status"] == W.QP_INFEASIBLE
+    print("latched" if latch else "unlatched", "OK", n_ok, "INFEASIBLE", n_inf, "of", 2 * n)
+    assert n_ok == 2 * n if latch else (n_ok >= 0.1 * 2 * n and n_inf >= 0.1 * 2 * n and n_ok + n_inf == 2 * n)
+
+
+def test_c_normals_under_the_host_sanitizers(tmp_path):
+    """oracle/wbc_ref.c with the stand-alone driver oracle/sanitize_normals_main.c, compiled with
+    -fsanitize=address,undefined (oracle/Makefile `sanitize`) and run once: one robot per QP form through
+    30 cycles of a mask-changing sequence with normals set, replaced and cleared.  A program of its own on
+    the CPU; a sanitizer report ends it with a non-zero status."""
+    import subprocess
+
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "sanitize", f"SAN_OUT={tmp_path}/sanitize_normals"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "sanitize_normals: done" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

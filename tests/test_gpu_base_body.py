@@ -17,6 +17,7 @@ import pytest
 
 import base_body_oracle as BB
 import contact_normals_oracle as CN
+import stateful_sequences as S
 import wbc_ref as R
 from quadrupedwholebodycontroller_amd import (COLD, DEBUG, FUSED, GROUP, QP_NUMERIC, QP_OK, RESIDENT, SPLIT, STATELESS, Engine,
                                               WbcError, split_debug, workloads)
@@ -281,6 +282,66 @@ def test_device_bound_table_with_invalid_rows():
         for k in ("tau", "grf", "x"):
             assert not out[k][rows_bad].any(), k
         assert_identical(out, ref, idx_a=others, idx_b=others, what=("others", flags))
+
+
+# 8b ---------------------------------------------------------------------------------------------
+def test_device_bound_row_invalid_for_one_cycle():
+    """A device-bound table in a stateful run (B = 8, the first 40 cycles of the latched off-trot sequence of
+    tests/stateful_sequences.py) whose row for robot 3 holds a NaN CoM on cycle 20 only: that robot returns
+    WBC_QP_NUMERIC and zeros on that cycle, and every other robot has, on all 40 cycles, the bits of a run
+    whose table never held the bad row.
+
+    What robot 3 returns after the row is valid again is recorded here and in DESIGN.md 18, not asserted
+    against an oracle (the reference has no such state): the flagged cycle marks the robot's first input
+    non-finite and its history takes that (e_int, Tdot_inv, the old Jacobian forms).  On MI355X, cycles
+    21..39, masks 0 0 0 4 4 4 0 0 0 5 5 5 0 0 0 6 6 6 0 with a latched change every third cycle: status
+    WBC_QP_OK on all 19; cycle 21 (all-swing, still reading Tdot_inv) non-finite tau and x; the other
+    all-swing cycles (22-23, 27-29, 33-35, 39) the clean run's bits; every cycle with a stance leg (24-26,
+    30-32, 36-38) non-finite tau and x, through W's ki * e_int term.  The test prints this record.  A reset
+    of the robot clears it: after cycle 39 robot 3 is reset in both runs, and six more cycles must give both
+    runs the same bits on every robot (asserted: engine against engine)."""
+    torch = pytest.importorskip("torch")
+    B, steps, at, who, more = 8, 40, 20, 3, 6
+    rows = BB.payload_rows(B)
+    seq = S.sequence(B, 3, 5, True)[:steps + more]
+    runs = {}
+    for name in ("clean", "bad"):
+        d = torch.from_numpy(np.ascontiguousarray(rows)).cuda()
+        torch.cuda.synchronize()
+        e = Engine(B)
+        e.bind_device_base_body(d)
+        outs = []
+        for k, s in enumerate(seq):
+            if name == "bad" and k in (at, at + 1):
+                d[who, 2] = float("nan") if k == at else float(rows[who, 2])
+                torch.cuda.synchronize()
+            if k == steps:
+                e.reset((np.arange(B) == who).astype(np.uint8))
+            e.set_state(s["base_pose"], s["nu"], s["qj"])
+            e.set_reference(s["ref"], s["contacts"], s["switching"])
+            e.step(0)
+            outs.append(e.outputs())
+        e.close()
+        runs[name] = {k: np.array([o[k] for o in outs]) for k in ("tau", "grf", "x", "status", "iters")}
+    clean, bad = runs["clean"], runs["bad"]
+    assert np.sum(clean["status"] == QP_OK) >= 0.9 * steps * B
+    assert bad["status"][at, who] == QP_NUMERIC
+    for k in ("tau", "grf", "x"):
+        assert not bad[k][at, who].any(), k
+    others = np.arange(B) != who
+    for k in ("tau", "grf", "x", "status", "iters"):
+        assert np.array_equal(bad[k][:, others], clean[k][:, others]), k
+        assert np.array_equal(bad[k][:at, who], clean[k][:at, who]), k
+        assert np.array_equal(bad[k][steps:], clean[k][steps:]), (k, "after the reset")
+    assert np.isfinite(bad["tau"][steps:]).all() and np.isfinite(bad["x"][steps:]).all()
+    after = bad["status"][at + 1:steps, who]
+    kinds = "".join("=" if all(np.array_equal(bad[k][c, who], clean[k][c, who]) for k in ("tau", "grf", "x", "status", "iters"))
+                    else "n" if not (np.isfinite(bad["tau"][c, who]).all() and np.isfinite(bad["x"][c, who]).all()) else "d"
+                    for c in range(at + 1, steps))
+    print(f"robot {who}, cycles {at + 1}..{steps - 1} (= the clean run's bits, d finite but different, n not finite): {kinds}; "
+          f"status {after.tolist()}, clean {clean['status'][at + 1:steps, who].tolist()}; masks {[int(s['contacts'][who]) for s in seq[at:steps]]}, "
+          f"switching {[int(s['switching'][who]) for s in seq[at:steps]]}; "
+          f"worst |tau - clean| on the d cycles {max([np.abs(bad['tau'][c, who] - clean['tau'][c, who]).max() for c in range(at + 1, steps) if kinds[c - at - 1] == 'd'], default=0.0):.3g}")
 
 
 # 9 ----------------------------------------------------------------------------------------------

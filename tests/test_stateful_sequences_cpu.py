@@ -176,3 +176,75 @@ def test_numpy_and_c_oracle_agree_on_stateful_intermediates():
                 assert M.record(f"oracle spread {q}", rel_err(x, y), tol) <= tol, (latch, k, q)
             if c["status"] == W.QP_OK:
                 assert M.record("oracle spread tau", rel_err(c["tau"], np_robot.tau), M.TAU) <= M.TAU, (latch, k)
+
+
+# The table combinations of tests/test_gpu_stateful_offtrot.py::test_tables, on the oracle alone ---------
+import pytest  # noqa: E402
+
+import test_gpu_stateful_offtrot as OT  # noqa: E402  (its oracle(), cache and COMBOS: importing it needs no GPU)
+
+# each combination with one of its tables taken out: what that table must move
+LESS = {"normals": {"normals": {}}, "payload": {"payload": {}},
+        "params_normals": {"params": dict(nrm=5), "normals": dict(tab=11)},
+        "all_three": {"params": dict(nrm=5, bb=11), "normals": dict(tab=11, bb=11), "payload": dict(tab=11, nrm=5)}}
+
+
+@pytest.mark.parametrize("combo", list(OT.COMBOS))
+def test_table_combinations_on_the_oracle(combo):
+    """What the GPU cases of a table combination rest on, shown by the C oracle before any GPU run, with
+    the seeds the issue of those cases names (table(8, 11), normals(8, 5, 0.35), payload_rows(8): none had
+    to be changed):
+      * latched, at least 0.9 of the 6 144 solves are OK; unlatched, at least 0.1 are OK, at least 0.1
+        INFEASIBLE, and there is no third status;
+      * LITERAL and REDUCED agree on every status;
+      * every table in force matters: with it taken out, tau moves by more than 1e-3 N m on at least half
+        of the rows that are OK in both runs (latched);
+      * the oracles' own spread on tau, x and grf in the GPU tests' measure, recorded and held to the
+        bounds the engine is held to: LITERAL against REDUCED, and REDUCED against itself with every
+        input moved by at most one ulp."""
+    kw, n = OT.COMBOS[combo], STEPS * B
+    for latch in (True, False):
+        tag = "latched" if latch else "unlatched"
+        lit, red, ulp = (OT.oracle(latch, R.LITERAL, **kw), OT.oracle(latch, R.REDUCED, **kw),
+                         OT.oracle(latch, R.REDUCED, ulp=0, **kw))
+        assert lit["status"].shape == (STEPS, B)
+        n_ok, n_inf = int(np.sum(lit["status"] == W.QP_OK)), int(np.sum(lit["status"] == W.QP_INFEASIBLE))
+        print(combo, tag, "OK", n_ok, "INFEASIBLE", n_inf, "of", n)
+        if latch:
+            assert n_ok >= 0.9 * n and n_ok + n_inf == n, (n_ok, n_inf)
+        else:
+            assert n_ok >= 0.1 * n and n_inf >= 0.1 * n and n_ok + n_inf == n, (n_ok, n_inf)
+        assert np.array_equal(lit["status"], red["status"]), tag
+        ok = lit["status"] == W.QP_OK
+        ok_ulp = ok & (ulp["status"] == W.QP_OK)
+        assert ok_ulp.sum() >= 0.99 * ok.sum()
+        for q, bound in OT.TABLE_TOLS.items():
+            forms = np.where(ok, OT.norm_err(red[q], lit[q]), 0.0).max()
+            moved = np.where(ok_ulp, OT.norm_err(ulp[q], red[q]), 0.0).max()
+            assert M.record(f"oracle spread {q}, {combo}, {tag}, LITERAL vs REDUCED", forms, bound) <= bound
+            assert M.record(f"oracle spread {q}, {combo}, {tag}, inputs moved by an ulp", moved, bound) <= bound
+    lit = OT.oracle(True, R.LITERAL, **kw)
+    for name, less in LESS[combo].items():
+        other = OT.oracle(True, R.LITERAL, **less)
+        both = (lit["status"] == W.QP_OK) & (other["status"] == W.QP_OK)
+        frac = np.mean((np.abs(lit["tau"] - other["tau"]).max(axis=-1) > 1e-3)[both])
+        print(combo, ": without the", name, "table tau moves on", f"{frac:.3f}", "of", int(both.sum()), "rows")
+        assert both.sum() >= 0.9 * n and frac >= 0.5, (name, frac)
+
+
+def test_the_swap_and_the_reset_change_the_oracle_run():
+    """The oracle halves of test_tables_swapped_at_an_unlatched_mask_change and test_reset_under_tables:
+    cycle 300 is a mask change for every robot, the swapped run equals the unswapped one before it and
+    differs from it there on every robot, and the reset changes robots 1, 4 and 6 alone."""
+    kw = OT.COMBOS["all_three"]
+    seq = S.sequence(B, DWELL, SEED, False)
+    assert OT.SWAP_AT == OT.RESET_AT == 300 and np.all(seq[299]["contacts"] != seq[300]["contacts"])
+    plain, swapped = OT.oracle(False, R.LITERAL, **kw), OT.oracle(False, R.LITERAL, swap=True, **kw)
+    for q in OT.STATEFUL_Q + ("tau", "status"):
+        assert np.array_equal(plain[q][:300], swapped[q][:300]), q
+    for b in range(B):
+        assert any(np.any(plain[q][300, b] != swapped[q][300, b]) for q in ("r1", "rsw")), b
+    plain, reset = OT.oracle(True, R.LITERAL, **kw), OT.oracle(True, R.LITERAL, reset=True, **kw)
+    for b in range(B):
+        changed = any(np.any(plain[q][300, b] != reset[q][300, b]) for q in OT.STATEFUL_Q)
+        assert changed == (b in OT.RESET_ROBOTS), b
