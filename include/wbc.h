@@ -17,6 +17,7 @@
  *   controlLoop() body (update; solve; torques) cpp:650-652       -> wbc_step (fused)
  *   jointTorquePub_/desiredGroundReactionForcesPub_ cpp:563,576   -> wbc_get_output
  *   qpReturnValue_ != SUCCESSFUL_RETURN          cpp:654           -> per-robot status[] (WBC_QP_*)
+ *   qpOASES getObjVal() of the solver of cpp:517-533               -> wbc_get_objective (wbc_step_modes, WBC_OBJECTIVE)
  *
  * Conventions
  *  - Everything is fp64.  Sizes are compile-time constants of the reference (hpp:27-32).
@@ -124,6 +125,10 @@ enum {
                           * ends after 100 ms without a cycle, or at any other call on the engine (which
                           * waits for it); the next WBC_RESIDENT cycle starts it again.  Same results as a
                           * plain wbc_cycle. */
+#define WBC_OBJECTIVE 512u /* wbc_step_modes only (default form): also write each hypothesis' QP objective at its
+                          * optimum (wbc_get_objective / wbc_device_objective) */
+#define WBC_BEST 1024u   /* wbc_step_modes only (default form), implies WBC_OBJECTIVE: after the step, choose each
+                          * state's best feasible hypothesis (wbc_get_best_modes / wbc_device_best_modes) */
 
 /* Debug record layout (doubles per robot), written by update/step under WBC_DEBUG. */
 enum {
@@ -245,6 +250,30 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags);
  * wbc_set_modes from the batch and the device's CU count (WBC_MODES_M in the environment overrides
  * it with a divisor of n_modes).  Results are bit-identical either way. */
 int32_t wbc_modes_per_wave(wbc_engine* h, int32_t* m);
+/* Which hypothesis to use: the QP's own objective at the optimum, what qpOASES' getObjVal() returns for
+ * the reference's problem (cpp:466-515: H = S^T Jc,com Jc,com^T S + R, R = diag(I_30, slack_weight I_12),
+ * g = -S^T Jc,com W),
+ *     obj = 1/2 x^T H x + g^T x
+ *         = 1/2 (|a|^2 + |qdd|^2 + |f|^2 + slack_weight |s|^2) + 1/2 |E^T f|^2 - W . (E^T f),
+ * with x = [a; qdd; f; s], E^T f = (sum_l f_l, sum_l d_l x f_l) over the stance legs and W the desired
+ * wrench (cpp:426-445), formed in the solve where those live.
+ * wbc_step_modes(flags | WBC_OBJECTIVE) also writes obj[s * K + k], laid out as the other outputs;
+ * a hypothesis whose status is not WBC_QP_OK has obj = +infinity (its other outputs are zero as ever).
+ * WBC_NO_X is allowed and does not change the objective's bits; tau, grf, x, status and iters are
+ * bit-identical to a step without the flag.  WBC_BEST (implies WBC_OBJECTIVE) then chooses per state
+ * s the index k into modes[] (not the mask) of the lowest objective among its WBC_QP_OK hypotheses
+ * (compared as doubles, a tie to the lowest k) and gathers that row's tau and grf, bit for bit, into
+ * [S][12] arrays, with the objective in obj[s]; a state with no OK hypothesis has best = -1,
+ * obj = +infinity, zero tau and grf.  wbc_get_best_modes: any pointer may be NULL.
+ * The buffers are the engine's own, allocated at the first step that carries a flag, and written on the
+ * engine's stream as the other outputs are (the device pointers stay valid until wbc_destroy).  The
+ * getters return WBC_ERR_STATE unless the last wbc_step_modes carried the matching flag.  Either
+ * flag with WBC_SPLIT, or on wbc_step / wbc_update / wbc_solve / wbc_cycle, is WBC_ERR_ARG. */
+int32_t wbc_get_objective(wbc_engine* h, double* obj /* [B] */);
+int32_t wbc_device_objective(wbc_engine* h, double** d_obj);
+int32_t wbc_get_best_modes(wbc_engine* h, int32_t* best /* [S] */, double* obj /* [S] */, double* tau /* [S][12] */,
+                           double* grf /* [S][12] */);
+int32_t wbc_device_best_modes(wbc_engine* h, int32_t** d_best, double** d_obj, double** d_tau, double** d_grf);
 
 /* Per-robot controller parameters (an RL batch with randomised friction, actuator limit and gains;
  * a sweep over gains): a table of doubles, row-major [B][WBC_RP_LEN], row b for robot b.  Rows are

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("WBC_LIB", os.path.join(HERE, "libwbc_hip.so"))
 NUM_JOINTS, NV, NC = 12, 42, 70
 POSE_LEN, NU_LEN, REF_LEN = 7, 18, 54
 STATELESS, DEBUG, NO_X, SPLIT, TIMED, COLD, FUSED, GROUP, RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128, 256
+# wbc_step_modes only: each hypothesis' QP objective; the best feasible hypothesis per state (implies OBJECTIVE)
+OBJECTIVE, BEST = 512, 1024
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
 # columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
 ROBOT_PARAM_NAMES = ("friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing", "slack_weight")
@@ -34,6 +36,8 @@ BB_COLUMN_NAMES = ("mass", "com_x", "com_y", "com_z", "I_xx", "I_xy", "I_xz", "I
 # wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
 TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN}
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
+# the objective and best-mode outputs of wbc_step_modes (WBC_OBJECTIVE / WBC_BEST)
+MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
 
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
@@ -44,7 +48,7 @@ C_API_SYMBOLS = [
     "wbc_default_params", "wbc_anymal_model", "wbc_create", "wbc_destroy", "wbc_batch", "wbc_set_stream",
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
-    "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS,
+    "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS,
 ]
 
 
@@ -114,9 +118,13 @@ def load_library(path: str = LIB_PATH):
         "wbc_last_error": ([], C.c_char_p),
         "wbc_model_from_urdf": ([C.c_char_p, P, P, C.c_char_p, C.POINTER(WbcModel)], I32),
         **{name: ([P, P], I32) for name in TABLE_SYMBOLS},
+        "wbc_get_objective": ([P, P], I32),
+        "wbc_device_objective": ([P, C.POINTER(P)], I32),
+        "wbc_get_best_modes": ([P, P, P, P, P], I32),
+        "wbc_device_best_modes": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)], I32),
     }
     for name, (argt, rest) in sig.items():
-        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS) and not hasattr(lib, name):
+        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS) and not hasattr(lib, name):
             continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -515,6 +523,33 @@ class Engine:
         ptrs = [C.c_void_p() for _ in range(5)]
         self._check(self.lib.wbc_device_outputs(self.h, *[C.byref(p) for p in ptrs]), "wbc_device_outputs")
         return dict(zip(("tau", "grf", "x", "status", "iters"), (p.value for p in ptrs)))
+
+    def objective(self) -> np.ndarray:
+        """wbc_get_objective: (B,) QP objective of each hypothesis after step_modes(... | OBJECTIVE), row
+        s * K + k as the other outputs; +inf where status is not QP_OK."""
+        obj = np.zeros(self.batch)
+        self._check(self.lib.wbc_get_objective(self.h, _ptr(obj)), "wbc_get_objective")
+        return obj
+
+    def device_objective(self) -> int:
+        """wbc_device_objective: the device address of the (B,) objectives."""
+        p = C.c_void_p()
+        self._check(self.lib.wbc_device_objective(self.h, C.byref(p)), "wbc_device_objective")
+        return p.value
+
+    def best_modes(self):
+        """wbc_get_best_modes after step_modes(... | BEST): per state the index into the modes of its best
+        feasible hypothesis (-1: none), that hypothesis' objective (+inf: none), tau and grf."""
+        S = self.input_rows
+        best = np.zeros(S, np.int32); obj = np.zeros(S); tau = np.zeros((S, NUM_JOINTS)); grf = np.zeros((S, NUM_JOINTS))
+        self._check(self.lib.wbc_get_best_modes(self.h, _ptr(best), _ptr(obj), _ptr(tau), _ptr(grf)), "wbc_get_best_modes")
+        return dict(best=best, objective=obj, tau=tau, grf=grf)
+
+    def device_best_modes(self):
+        """wbc_device_best_modes: the device addresses of best (int32 [S]), objective [S], tau and grf [S, 12]."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.lib.wbc_device_best_modes(self.h, *[C.byref(p) for p in ptrs]), "wbc_device_best_modes")
+        return dict(zip(("best", "objective", "tau", "grf"), (p.value for p in ptrs)))
 
     def debug(self):
         out = np.zeros((self.batch, DBG["LEN"]))

@@ -35,6 +35,11 @@ static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t)
 #undef X
 static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_ALL_INSTANCES, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
+// the mode loop's objective instance (wbc_kernel_modes_obj.hip) and the selection after it (WBC_BEST)
+extern "C" hipError_t wbc_launch_modes_obj(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_best_modes(const double* obj, const int32_t* status, const double* tau, const double* grf,
+                                            int states, int modes, int32_t* best, double* bobj, double* btau, double* bgrf,
+                                            hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
 extern "C" hipError_t wbc_preload_resident();
@@ -117,6 +122,15 @@ struct wbc_engine {
     // and the hypotheses' order, chunk by chunk (plan_mode_loop)
     int32_t mode_loop = 1;
     uint8_t mode_order[16] = {};
+    // wbc_step_modes with WBC_OBJECTIVE / WBC_BEST: the hypotheses' objectives [B] and, per state (at
+    // most B of them), the best hypothesis, its objective, tau and grf; allocated at the first step that
+    // carries the flag.  modes_flags: which of the two flags the last wbc_step_modes carried
+    double* d_obj = nullptr;
+    int32_t* d_best = nullptr;
+    double* d_best_obj = nullptr;
+    double* d_best_tau = nullptr;
+    double* d_best_grf = nullptr;
+    uint32_t modes_flags = 0;
     // bound (possibly external) inputs
     wbc::ConstInputView in{};
     // state / outputs
@@ -216,6 +230,7 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.nwaves = (h->batch + wbc::QMAP_SEG - 1) / wbc::QMAP_SEG;
     a.mloop = 0;
     std::memset(a.mode_order, 0, sizeof(a.mode_order));
+    a.obj = nullptr;
     return a;
 }
 wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) { return make_args(h, flags, h->in, h->out); }
@@ -419,6 +434,13 @@ int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uin
     }
     return WBC_OK;
 }
+
+// WBC_OBJECTIVE and WBC_BEST belong to wbc_step_modes' default form; every other call refuses them
+constexpr uint32_t kModeOutFlags = WBC_OBJECTIVE | WBC_BEST;
+int32_t refuse_mode_out_flags(const char* call, uint32_t flags) {
+    if (!(flags & kModeOutFlags)) return WBC_OK;
+    return fail(WBC_ERR_ARG, std::string(call) + ": WBC_OBJECTIVE / WBC_BEST are wbc_step_modes flags");
+}
 }  // namespace
 
 extern "C" {
@@ -559,7 +581,8 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_box) (void)hipHostFree(h->res_box);
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
-                    h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat};
+                    h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
+                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -826,6 +849,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_update", flags, 0, "default wbc_step only")) return rc;
+    if (const int32_t rc = refuse_mode_out_flags("wbc_update", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -839,6 +863,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_solve: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_solve", flags, 0, "default wbc_step only")) return rc;
+    if (const int32_t rc = refuse_mode_out_flags("wbc_solve", flags)) return rc;
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
@@ -852,6 +877,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     WBC_HIP(sync_own(h));
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_step", flags, WBC_SPLIT | WBC_FUSED, "default form only")) return rc;
+    if (const int32_t rc = refuse_mode_out_flags("wbc_step", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags, io.in, io.out);
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
@@ -893,6 +919,7 @@ int32_t wbc_set_modes(wbc_engine* h, int32_t n_modes, const uint8_t* modes) {
     // contacts[] copied while modes were set hold S rows only: the engine's own masks get their
     // wave map on the device from here on, until the next wbc_set_reference / wbc_cycle with masks
     h->qmap_host = false;
+    h->modes_flags = 0;  // the objective and best-mode buffers describe the previous hypotheses
     if (n_modes == 0) {
         h->n_modes = 0;
         return WBC_OK;
@@ -917,7 +944,19 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_tables(h, "wbc_step_modes", flags, 0, "default wbc_step only")) return rc;
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
+    const uint32_t mode_out = (flags & WBC_BEST) ? kModeOutFlags : (flags & WBC_OBJECTIVE);  // WBC_BEST implies WBC_OBJECTIVE
+    if (mode_out && (flags & WBC_SPLIT))
+        return fail(WBC_ERR_ARG, "wbc_step_modes: WBC_OBJECTIVE / WBC_BEST belong to the default form (not WBC_SPLIT)");
     WBC_HIP(hipSetDevice(h->device));
+    const size_t B = (size_t)h->batch;
+    if (mode_out && !h->d_obj) WBC_HIP(dalloc(&h->d_obj, B));
+    if ((mode_out & WBC_BEST) && !h->d_best_grf) {  // (the last of the four: a failed allocation is tried again)
+        if (!h->d_best) WBC_HIP(dalloc(&h->d_best, B));
+        if (!h->d_best_obj) WBC_HIP(dalloc(&h->d_best_obj, B));
+        if (!h->d_best_tau) WBC_HIP(dalloc(&h->d_best_tau, B * WBC_NUM_JOINTS));
+        WBC_HIP(dalloc(&h->d_best_grf, B * WBC_NUM_JOINTS));
+    }
+    h->modes_flags = 0;
     wbc::KernelArgs a = make_args(h, flags);
     a.modes = h->n_modes;
     const bool timed = (flags & WBC_TIMED) != 0;
@@ -930,15 +969,24 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
         au.batch = h->batch / h->n_modes;
         WBC_HIP(wbc_launch_update(&au, h->stream));
         WBC_HIP(launch_solves(h, a));
-    } else if (h->mode_loop > 1) {
-        // default, many states: one update per state and wave, then mode_loop hypotheses in turn
+    } else if (h->mode_loop > 1 || mode_out) {
+        // default, many states: one update per state and wave, then mode_loop hypotheses in turn; with
+        // WBC_OBJECTIVE / WBC_BEST the loop's objective instance at every mode_loop, 1 included
         a.elim = 1;
         h->elim = false;
         a.mloop = h->mode_loop;
         std::memcpy(a.mode_order, h->mode_order, sizeof(a.mode_order));
         const int64_t S = h->batch / h->n_modes;
         a.nwaves = (int32_t)(((S + wbc::QMAP_SEG - 1) / wbc::QMAP_SEG) * (h->n_modes / h->mode_loop));
-        WBC_HIP(wbc_launch_modes(&a, h->stream));
+        if (mode_out) {
+            a.obj = h->d_obj;
+            WBC_HIP(wbc_launch_modes_obj(&a, h->stream));
+            if (mode_out & WBC_BEST)
+                WBC_HIP(wbc_launch_best_modes(a.obj, a.status, a.tau, a.grf, (int)S, h->n_modes, h->d_best, h->d_best_obj,
+                                              h->d_best_tau, h->d_best_grf, h->stream));
+        } else {
+            WBC_HIP(wbc_launch_modes(&a, h->stream));
+        }
     } else {
         // default: each hypothesis reduced and solved in its own 16-lane segment
         WBC_HIP(begin_step16(h, a, flags, h->d_qmap));
@@ -949,6 +997,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
         h->timed = true;
     }
     h->updated = false;
+    h->modes_flags = mode_out;
     return WBC_OK;
 }
 
@@ -1056,6 +1105,7 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_cycle: mode hypotheses are set");
     if (!base_pose || !nu || !qj || !ref || !contacts || !switching) return fail(WBC_ERR_ARG, "wbc_cycle: null input");
     if (const int32_t rc = refuse_tables(h, "wbc_cycle", flags, WBC_SPLIT | WBC_FUSED | WBC_RESIDENT, "plain cycle only")) return rc;
+    if (const int32_t rc = refuse_mode_out_flags("wbc_cycle", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     if (!h->h_in) {
@@ -1147,6 +1197,46 @@ int32_t wbc_get_debug(wbc_engine* h, double* out) {
     WBC_HIP(hipSetDevice(h->device));
     WBC_HIP(hipMemcpyAsync(out, h->d_dbg, (size_t)h->batch * WBC_DBG_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     WBC_HIP(hipStreamSynchronize(h->stream));
+    return WBC_OK;
+}
+
+int32_t wbc_get_objective(wbc_engine* h, double* obj) {
+    if (!h || !obj) return fail(WBC_ERR_ARG, "null argument");
+    if (!(h->modes_flags & WBC_OBJECTIVE)) return fail(WBC_ERR_STATE, "wbc_get_objective: the last wbc_step_modes did not carry WBC_OBJECTIVE");
+    WBC_HIP(hipSetDevice(h->device));
+    WBC_HIP(hipMemcpyAsync(obj, h->d_obj, (size_t)h->batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));
+    return WBC_OK;
+}
+
+int32_t wbc_device_objective(wbc_engine* h, double** d_obj) {
+    if (!h || !d_obj) return fail(WBC_ERR_ARG, "null argument");
+    if (!(h->modes_flags & WBC_OBJECTIVE)) return fail(WBC_ERR_STATE, "wbc_device_objective: the last wbc_step_modes did not carry WBC_OBJECTIVE");
+    *d_obj = h->d_obj;
+    return WBC_OK;
+}
+
+int32_t wbc_get_best_modes(wbc_engine* h, int32_t* best, double* obj, double* tau, double* grf) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (!(h->modes_flags & WBC_BEST)) return fail(WBC_ERR_STATE, "wbc_get_best_modes: the last wbc_step_modes did not carry WBC_BEST");
+    WBC_HIP(hipSetDevice(h->device));
+    const size_t S = input_rows(h);
+    hipStream_t st = h->stream;
+    if (best) WBC_HIP(hipMemcpyAsync(best, h->d_best, S * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (obj) WBC_HIP(hipMemcpyAsync(obj, h->d_best_obj, S * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) WBC_HIP(hipMemcpyAsync(tau, h->d_best_tau, S * WBC_NUM_JOINTS * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (grf) WBC_HIP(hipMemcpyAsync(grf, h->d_best_grf, S * WBC_NUM_JOINTS * sizeof(double), hipMemcpyDeviceToHost, st));
+    WBC_HIP(hipStreamSynchronize(st));
+    return WBC_OK;
+}
+
+int32_t wbc_device_best_modes(wbc_engine* h, int32_t** d_best, double** d_obj, double** d_tau, double** d_grf) {
+    if (!h) return fail(WBC_ERR_ARG, "null handle");
+    if (!(h->modes_flags & WBC_BEST)) return fail(WBC_ERR_STATE, "wbc_device_best_modes: the last wbc_step_modes did not carry WBC_BEST");
+    if (d_best) *d_best = h->d_best;
+    if (d_obj) *d_obj = h->d_best_obj;
+    if (d_tau) *d_tau = h->d_best_tau;
+    if (d_grf) *d_grf = h->d_best_grf;
     return WBC_OK;
 }
 

@@ -1762,7 +1762,10 @@ __device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]
 #pragma unroll
     for (int r = 0; r < 3; ++r) e[r] = CN ? seg_shfl(cnf[r], p & 15) : 0.0;
 }
-template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false>
+// OBJ (the mode loop's objective instance, wbc_kernel_modes_obj.hip): the output stage also forms the
+// QP's objective at the optimum, 1/2 x^T H x + g^T x in its closed form, from the x it
+// forms whether or not KernelArgs::x is bound, and stores it to KernelArgs::obj (+infinity unless OK)
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
                         double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr) {
@@ -2326,11 +2329,11 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
             a.grf[(size_t)qp * 12 + l] = (ok && stl) ? x : 0.0;
         }
     }
-    if (a.x) {  // the 42-vector's maps read z from LDS
+    if (OBJ || a.x) {  // the 42-vector's maps read z from LDS
         if (l < N) V.f[l] = x;
         lds_sync();
     }
-    if (a.x && wr) {  // x (42, cpp:534-541): a = Mb^-1 (E_S^T f) - g e_z, qdd, f, slacks
+    if ((OBJ || a.x) && wr) {  // x (42, cpp:534-541): a = Mb^-1 (E_S^T f) - g e_z, qdd, f, slacks
         double F[3] = {0, 0, 0}, Mm[3] = {0, 0, 0};
 #pragma unroll
         for (int ll = 0; ll < 4; ++ll) {
@@ -2363,10 +2366,13 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
 #pragma unroll
             for (int c = 0; c < 6; ++c) phi[c] = -bf[c];
         }
+        [[maybe_unused]] double oc = 0.0;  // OBJ: the lane's share of the objective
         if (l < 12) {
             double* xr = a.x + (size_t)qp * WBC_NV;
+            if constexpr (!OBJ) {
             if (l < 6) xr[l] = ok ? ((l < 3) ? sel3(bf, l < 3 ? l : 0) - (l == 2 ? pr.gravity : 0.0)
                                              : sel3(&bf[3], l < 3 ? 0 : l - 3)) : 0.0;
+            }
             double qv = V.q0[l];
 #pragma unroll
             for (int c = 0; c < 6; ++c) qv = fma(V.Y[l * 6 + c], phi[c], qv);
@@ -2383,9 +2389,40 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     sv = fabs(r);
                 }
             }
+            if constexpr (!OBJ) {
             xr[6 + l] = ok ? qv : 0.0;
             xr[18 + l] = (ok && stl) ? V.f[l] : 0.0;
             xr[30 + l] = ok ? sv : 0.0;
+            } else {
+                // the objective instance forms x whether or not the array is bound, stores it when it is
+                const double av = ok ? ((l < 3) ? sel3(bf, l < 3 ? l : 0) - (l == 2 ? pr.gravity : 0.0)
+                                                : sel3(&bf[3], l < 3 ? 0 : l - 3)) : 0.0;
+                const double fx = (ok && stl) ? V.f[l] : 0.0;
+                if (a.x) {
+                    if (l < 6) xr[l] = av;
+                    xr[6 + l] = ok ? qv : 0.0;
+                    xr[18 + l] = fx;
+                    xr[30 + l] = ok ? sv : 0.0;
+                }
+                // 1/2 (|a|^2 + |qdd|^2 + |f|^2 + w |s|^2): lane l's entries of the four blocks
+                const double a2 = (l < 6) ? av * av : 0.0;
+                oc = 0.5 * (fma(pr.slack_weight * sv, sv, fma(fx, fx, fma(qv, qv, a2))));
+            }
+        }
+        if constexpr (OBJ) {
+            // + 1/2 |E^T f|^2 - W . E^T f with E^T f = (F, Mm), once per segment (lane 0), then the
+            // segment sum; the value is the same in every lane of the segment
+            double ef = 0.0, wf = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                ef = fma(F[c], F[c], ef);
+                ef = fma(Mm[c], Mm[c], ef);
+                wf = fma(P.W[c], F[c], wf);
+                wf = fma(P.W[3 + c], Mm[c], wf);
+            }
+            if (l == 0) oc += fma(0.5, ef, -wf);
+            const double ov = seg_sum<16>(oc);
+            if (l == 0) a.obj[qp] = ok ? ov : __builtin_inf();
         }
     }
     if (wr && l == 0) {
@@ -2450,7 +2487,7 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false, bool BB = false>
+          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
@@ -3267,13 +3304,13 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             if (km == 15) {  // stateless mask 15: the four-contact stance form
                 double hrow[12], gsv = 0.0;
                 ok = stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane);
-                if (ok) solve16<true, false, STF>(a, rb, q, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK);
+                if (ok) solve16<true, false, STF, false, false, OBJ>(a, rb, q, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK);
             } else {
                 const St16 V(s, P, fric);
                 bool vac = false;
                 ok = reduce_general(a, rb, P, pr, lane, km, s, V, vac);
-                if (ok) solve16<true, true, STF>(a, rb, q, lane, wr, P, s, V, km, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
-                                                 hWlo, hWhi, hWtag);
+                if (ok) solve16<true, true, STF, false, false, OBJ>(a, rb, q, lane, wr, P, s, V, km,
+                                                                    vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi, hWtag);
             }
             if (!ok && wr) {  // as wbc_update_solve_kernel's fallback record
                 lds_sync();
@@ -3670,7 +3707,8 @@ constexpr int PRE_FLAG = 90;  // packed index of Presolve::presolved
 static_assert(offsetof(Presolve, presolved) == PRE_FLAG * sizeof(double), "PRE_FLAG");
 static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing");
 
-template <bool CN = false>
+// OBJ: as solve16's (the objective from the recovered 42-vector, one entry per lane)
+template <bool CN = false, bool OBJ = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
@@ -4152,8 +4190,10 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
     STAMP(a, rb, 5);
     // outputs: x (42, cpp:534-541), grf = x[18:30] (cpp:556-563), tau (cpp:565-576)
     const bool ok = (status == WBC_QP_OK);
-    if (a.x && lane < 42) {
+    [[maybe_unused]] double oc = 0.0;  // OBJ: the lane's share of the objective
+    if ((OBJ || a.x) && lane < 42) {
         double xv;
+        [[maybe_unused]] double ew = 0.0;  // OBJ: 1/2 |E^T f|^2 - W . E^T f (lanes 0..5 hold F and Mm)
         if (lane < 6) {  // a = Mbar_b^-1 (Jc_com^T f - gw)
             double F[3] = {0, 0, 0}, Mm[3] = {0, 0, 0};
 #pragma unroll
@@ -4172,6 +4212,17 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
                 const int rr = lane - 3;
                 xv = P.Icinv[3 * rr] * Mm[0] + P.Icinv[3 * rr + 1] * Mm[1] + P.Icinv[3 * rr + 2] * Mm[2];
             }
+            if constexpr (OBJ) {
+                double ef = 0.0, wf = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    ef = fma(F[c], F[c], ef);
+                    ef = fma(Mm[c], Mm[c], ef);
+                    wf = fma(P.W[c], F[c], wf);
+                    wf = fma(P.W[3 + c], Mm[c], wf);
+                }
+                ew = fma(0.5, ef, -wf);
+            }
         } else if (lane < 18) {
             xv = yq[lane - 6];
         } else if (lane < 30) {
@@ -4181,7 +4232,19 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
             const int i = lane - 30;
             xv = ((kap >> (i / 3)) & 1) ? fabs(P.rsw[i]) : yq[12 + i];
         }
-        a.x[(size_t)rb * WBC_NV + lane] = ok ? xv : 0.0;
+        if (!OBJ || a.x) a.x[(size_t)rb * WBC_NV + lane] = ok ? xv : 0.0;
+        // 1/2 (|a|^2 + |qdd|^2 + |f|^2 + w |s|^2), entry by entry, and lane 0's wrench terms
+        if constexpr (OBJ) oc = fma(0.5 * (lane >= 30 ? pr.slack_weight : 1.0) * xv, xv, lane == 0 ? ew : 0.0);
+    }
+    if constexpr (OBJ) {
+        // the wave's sum: the four 16-lane rows (row_ror 8, 4, 2, 1), then their heads
+        double ov = oc;
+        ov += dpp_d<0x128>(ov);
+        ov += dpp_d<0x124>(ov);
+        ov += dpp_d<0x122>(ov);
+        ov += dpp_d<0x121>(ov);
+        ov = (bcast(ov, 0) + bcast(ov, 16)) + (bcast(ov, 32) + bcast(ov, 48));
+        if (lane == 0) a.obj[rb] = ok ? ov : __builtin_inf();
     }
     if (lane < 12) {
         double tv = P.bbj[lane];
@@ -4701,7 +4764,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
-template <bool CN = false>
+template <bool CN = false, bool OBJ = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -4710,10 +4773,11 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
+constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
 __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base, const double* r, bool bad) {
@@ -4748,7 +4812,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
-        solve_general_qp<fb_reads_cn(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -5060,7 +5124,17 @@ WBC_UPDATE_KERNEL_ATTR void wbc_resident_kernel(KernelArgs args, ResidentBox* bo
 // segment through one update and then the M hypotheses of chunk c (update_phase's mode loop);
 // the update's share of a hypothesis falls from one whole update to 1 / M of one.  Outputs,
 // fallbacks and their records are the per-hypothesis step's.
-WBC_UPDATE_KERNEL_ATTR void wbc_modes_kernel(KernelArgs a) {
+// WBC_MODES_OBJ (wbc_kernel_modes_obj.hip): the same loop as wbc_modes_obj_kernel, whose solves also
+// write each hypothesis' objective (solve16's OBJ; the fallback callee of its own, FB_MODES_OBJ); the
+// engine runs it for every M >= 1 when a step carries WBC_OBJECTIVE or WBC_BEST.
+#ifdef WBC_MODES_OBJ
+#define WBC_MODES_KERNEL wbc_modes_obj_kernel
+constexpr bool MODES_OBJ = true;
+#else
+#define WBC_MODES_KERNEL wbc_modes_kernel
+constexpr bool MODES_OBJ = false;
+#endif
+WBC_UPDATE_KERNEL_ATTR void WBC_MODES_KERNEL(KernelArgs a) {
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
     const int K = a.modes, M = a.mloop, C = K / M;
@@ -5075,12 +5149,12 @@ WBC_UPDATE_KERNEL_ATTR void wbc_modes_kernel(KernelArgs a) {
     stage_to_lds<LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
     lds_sync();
     unsigned fails = 0;
-    update_phase<UPD_SUB, true, LdsModel, true, 0>(a, row, row * K + k0, a.mode_masks[k0] & 15, lane, wr, L.u[seg],
-                                                L.prob[seg], nullptr, L.model, &L.fric[0], vin, c, &fails);
+    update_phase<UPD_SUB, true, LdsModel, true, 0, false, false, false, false, MODES_OBJ>(
+        a, row, row * K + k0, a.mode_masks[k0] & 15, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, c, &fails);
     for (int it = 0; it < M; ++it) {
         const unsigned long long fm = __ballot(wr && lane == 0 && ((fails >> it) & 1u));
         if (fm)
-            drain_fallbacks<fb_tag(FB_MODES)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm,
+            drain_fallbacks<fb_tag(MODES_OBJ ? FB_MODES_OBJ : FB_MODES)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm,
                                row * K + a.mode_order[c * M + it], reinterpret_cast<SolveLds*>(&L));
     }
 }
@@ -5092,7 +5166,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
-template <bool CN>
+template <bool CN, bool OBJ>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -5119,7 +5193,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
-template <bool CN>
+template <bool CN, bool OBJ>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -5146,7 +5220,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase<CN>(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN, OBJ>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5343,6 +5417,42 @@ __global__ __launch_bounds__(QMAP_THREADS) void wbc_qmap_scatter(const uint8_t* 
     for (int p = 4 * plan.waves + gt; p < cap; p += (int)gridDim.x * QMAP_THREADS) map[p] = QMAP_EMPTY;
 }
 
+// The best hypothesis per state after a wbc_step_modes with WBC_BEST: four states per
+// wave, one per 16-lane segment; lane k < K holds hypothesis k's objective (+infinity unless its status
+// is WBC_QP_OK).  The segment takes the exact minimum and the lowest lane holding it from a ballot (the
+// ratio test's form, 4.7), so a tie goes to the lowest k; lanes 0..11 then copy the winner's tau and grf
+// rows bit for bit.  No hypothesis OK: best = -1, objective +infinity, zero tau and grf.  A padding
+// segment recomputes the last state and writes nothing.
+__global__ __launch_bounds__(64) void wbc_best_mode_kernel(const double* obj, const int32_t* status, const double* tau,
+                                                           const double* grf, int S, int K, int32_t* best, double* bobj,
+                                                           double* btau, double* bgrf) {
+    const int seg = (int)threadIdx.x / UPD_SUB, l = (int)threadIdx.x % UPD_SUB;
+    int s = (int)blockIdx.x * UPD_RPW + seg;
+    const bool wr = s < S;
+    if (!wr) s = S - 1;
+    const bool has = l < K;
+    const size_t q = (size_t)s * K + (has ? l : 0);
+    const double o = obj[q];
+    const int st = status[q];
+    const double inf = __builtin_inf();
+    const double v = (has && st == WBC_QP_OK && o < inf) ? o : inf;
+    const double m = seg16_min(v);
+    const bool any = m < inf;
+    const unsigned hold = (unsigned)(__ballot(any && v == m) >> (seg * UPD_SUB)) & 0xFFFFu;
+    const int kb = any ? __builtin_ctz(hold | 0x10000u) : -1;
+    if (!wr) return;
+    if (l < 12) {
+        const size_t src = ((size_t)s * K + (kb < 0 ? 0 : kb)) * 12 + l;
+        const double tv = tau[src], gv = grf[src];
+        btau[(size_t)s * 12 + l] = any ? tv : 0.0;
+        bgrf[(size_t)s * 12 + l] = any ? gv : 0.0;
+    }
+    if (l == 0) {
+        best[s] = kb;
+        bobj[s] = m;
+    }
+}
+
 __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
     const int rb = xcd_robot();
     if (rb >= batch) return;
@@ -5369,10 +5479,17 @@ extern "C" hipError_t WBC_STEP_LAUNCHER(const wbc::KernelArgs* a, hipStream_t st
     return hipGetLastError();
 }
 #elif defined(WBC_MODES_TU)
-// The mode loop (wbc_kernel_modes.hip, Makefile MODES_KFLAGS)
-extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st) {
+// The mode loop (wbc_kernel_modes.hip, Makefile MODES_KFLAGS), and its objective instance
+// (wbc_kernel_modes_obj.hip, MODES_OBJ_KFLAGS), which needs KernelArgs::obj
+#ifdef WBC_MODES_OBJ
+#define WBC_MODES_LAUNCHER wbc_launch_modes_obj
+#else
+#define WBC_MODES_LAUNCHER wbc_launch_modes
+#endif
+extern "C" hipError_t WBC_MODES_LAUNCHER(const wbc::KernelArgs* a, hipStream_t st) {
     if (a->nwaves <= 0 || a->modes <= 0 || a->mloop <= 0 || a->modes % a->mloop != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(wbc::wbc_modes_kernel, dim3(a->nwaves), dim3(64), 0, st, *a);
+    if (wbc::MODES_OBJ && !a->obj) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wbc::WBC_MODES_KERNEL, dim3(a->nwaves), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 #elif defined(WBC_RESIDENT_TU)
@@ -5430,6 +5547,16 @@ extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStre
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st) {
     hipLaunchKernelGGL(wbc::wbc_solve_stance_kernel, dim3(a->batch), dim3(64), 0, st, *a);
     hipLaunchKernelGGL(wbc::wbc_solve_fallback_kernel, dim3(16), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+// The best hypothesis of each of S states over its K hypotheses' rows (wbc_step_modes with WBC_BEST)
+extern "C" hipError_t wbc_launch_best_modes(const double* obj, const int32_t* status, const double* tau, const double* grf,
+                                            int states, int modes, int32_t* best, double* bobj, double* btau, double* bgrf,
+                                            hipStream_t st) {
+    if (states <= 0 || modes <= 0 || modes > WBC_MAX_MODES || !obj || !status || !tau || !grf || !best || !bobj || !btau || !bgrf)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wbc::wbc_best_mode_kernel, dim3((states + wbc::UPD_RPW - 1) / wbc::UPD_RPW), dim3(64), 0, st, obj, status,
+                       tau, grf, states, modes, best, bobj, btau, bgrf);
     return hipGetLastError();
 }
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st) {

@@ -204,6 +204,11 @@ struct KernelArgs {
     // are contact-normal instances too: the engine points cn at a flat table of its own (and rp at its
     // uniform one) when no such table is in force.  After cn, so that no other argument's offset moves.
     const double* bb;
+    // The QP objective at the optimum per hypothesis (wbc_step_modes with WBC_OBJECTIVE / WBC_BEST):
+    // [batch], row qp for QP qp, +infinity where status is not WBC_QP_OK; written only by the mode loop's
+    // objective instance (wbc_kernel_modes_obj.hip) and its fallback solve.  After bb, so that no other
+    // argument's offset moves.
+    double* obj;
 };
 
 // ---------------------------------------------------------------------------------------
