@@ -18,6 +18,7 @@
  *   jointTorquePub_/desiredGroundReactionForcesPub_ cpp:563,576   -> wbc_get_output
  *   qpReturnValue_ != SUCCESSFUL_RETURN          cpp:654           -> per-robot status[] (WBC_QP_*)
  *   qpOASES getObjVal() of the solver of cpp:517-533               -> wbc_get_objective (wbc_step_modes, WBC_OBJECTIVE)
+ *   qpOASES getDualSolution() of the same solver, rows R2 and R3   -> wbc_get_duals (wbc_step, WBC_DUALS)
  *
  * Conventions
  *  - Everything is fp64.  Sizes are compile-time constants of the reference (hpp:27-32).
@@ -129,6 +130,8 @@ enum {
                           * optimum (wbc_get_objective / wbc_device_objective) */
 #define WBC_BEST 1024u   /* wbc_step_modes only (default form), implies WBC_OBJECTIVE: after the step, choose each
                           * state's best feasible hypothesis (wbc_get_best_modes / wbc_device_best_modes) */
+#define WBC_DUALS 2048u  /* wbc_step only (default form): also write each robot's QP multipliers of the friction
+                          * faces and torque limits (wbc_get_duals / wbc_device_duals) */
 
 /* Debug record layout (doubles per robot), written by update/step under WBC_DEBUG. */
 enum {
@@ -229,6 +232,40 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags);
 #define WBC_R_REL 1e-12
 int32_t wbc_step(wbc_engine* h, uint32_t flags);
 int32_t wbc_synchronize(wbc_engine* h);
+/* Which constraints bind, and how hard: the Lagrange multipliers of the QP's inequality rows that can be
+ * active at an optimum with positive price, the 16 friction faces (R2, cpp:404-424) and the 24 torque
+ * limits (R3, cpp:495,506,513), what qpOASES' getDualSolution() returns for those rows.
+ * wbc_step(flags | WBC_DUALS) in its default form also writes dual[b * WBC_DUAL_LEN + r] for robot b, in
+ * the row numbering the hotstart stores:
+ *     r = 4 leg + face              the friction faces, in the reference's R2 order
+ *     r = 16 + 2 j + side           joint j's torque rows: side 0 is tau_j >= -max_torque,
+ *                                   side 1 is tau_j <= +max_torque
+ * Each entry is the multiplier lambda_r >= 0 of the reference's row as the reference writes it (unscaled:
+ * the face (+-1, 0, mu) . f_l >= 0 in the foot's frame, the torque row in N m): the objective's rate of
+ * change per unit of relaxation of that row (a saturated actuator's lambda is what 1 N m more would buy).
+ * An entry is 0 for a row outside the final working set, for every face of a swing leg, and a robot
+ * whose status is not WBC_QP_OK has all 40 entries 0, like its other outputs.  At most 12 entries of a
+ * robot are non-zero.
+ * They are the multipliers of the same rows of the reference's 42 x 70 QP: the default step eliminates
+ * a, the swing slacks and the stance equalities exactly, which changes neither the
+ * objective's value nor these rows' slacks at any point, so the reduced QP's multipliers on them are the
+ * full QP's.  In qpOASES' sign convention (lbA <= A x <= ubA, H x + g = A^T y) they are y = -lambda on a
+ * friction row and on side 1 (upper bounds), y = +lambda on side 0 (a lower bound).  The other
+ * multipliers follow from x: of a swing leg's slack pair R4 / R5 (cpp:496-497,507-515), whichever row
+ * is tight carries slack_weight * s_i (stationarity in s_i), the other 0; the 18 equality multipliers
+ * (R0 / R1) are then fixed by stationarity, H x + g = A^T y, a least-squares fit of at most 18 unknowns
+ * to 42 equations whose residual certifies x: with primal feasibility, lambda >= 0 and lambda_r = 0 on
+ * slack rows it is the KKT system of a strictly convex QP, so x is its optimum.
+ * Allowed stateless, stateful and with WBC_COLD, with WBC_DEBUG, WBC_NO_X, WBC_TIMED and WBC_GROUP, and
+ * with any of the per-robot tables in force; tau, grf, x, status and iters are bit-identical to a step
+ * without the flag.  The buffer is the engine's own, allocated at the first step that carries the flag
+ * and written on the engine's stream as the other outputs are (the device pointer stays valid until
+ * wbc_destroy).  wbc_get_duals is synchronous.  Both getters return WBC_ERR_STATE unless the last
+ * wbc_step carried the flag.  WBC_DUALS with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, or on wbc_update /
+ * wbc_solve / wbc_cycle / wbc_step_modes, is WBC_ERR_ARG. */
+enum { WBC_DUAL_LEN = 40 };
+int32_t wbc_get_duals(wbc_engine* h, double* dual /* [B][40] */);
+int32_t wbc_device_duals(wbc_engine* h, double** d_dual);
 
 /* Contact-mode hypotheses (BASELINE configs[4]: every state solved under several contact masks).
  * After wbc_set_modes(h, K, modes) with K dividing the batch B, the engine holds S = B / K states:

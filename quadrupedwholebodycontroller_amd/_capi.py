@@ -18,6 +18,9 @@ POSE_LEN, NU_LEN, REF_LEN = 7, 18, 54
 STATELESS, DEBUG, NO_X, SPLIT, TIMED, COLD, FUSED, GROUP, RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128, 256
 # wbc_step_modes only: each hypothesis' QP objective; the best feasible hypothesis per state (implies OBJECTIVE)
 OBJECTIVE, BEST = 512, 1024
+# wbc_step only (default form): each robot's QP multipliers of the friction faces and torque limits
+DUALS = 2048
+DUAL_LEN = 40  # WBC_DUAL_LEN: rows 4 leg + face, then 16 + 2 joint + side (side 0: tau >= -max, side 1: tau <= +max)
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
 # columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
 ROBOT_PARAM_NAMES = ("friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing", "slack_weight")
@@ -38,6 +41,8 @@ TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
 # the objective and best-mode outputs of wbc_step_modes (WBC_OBJECTIVE / WBC_BEST)
 MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
+# the multipliers of wbc_step (WBC_DUALS)
+DUAL_SYMBOLS = ["wbc_get_duals", "wbc_device_duals"]
 
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
@@ -48,7 +53,7 @@ C_API_SYMBOLS = [
     "wbc_default_params", "wbc_anymal_model", "wbc_create", "wbc_destroy", "wbc_batch", "wbc_set_stream",
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
-    "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS,
+    "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS, *DUAL_SYMBOLS,
 ]
 
 
@@ -122,9 +127,11 @@ def load_library(path: str = LIB_PATH):
         "wbc_device_objective": ([P, C.POINTER(P)], I32),
         "wbc_get_best_modes": ([P, P, P, P, P], I32),
         "wbc_device_best_modes": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)], I32),
+        "wbc_get_duals": ([P, P], I32),
+        "wbc_device_duals": ([P, C.POINTER(P)], I32),
     }
     for name, (argt, rest) in sig.items():
-        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS) and not hasattr(lib, name):
+        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS, *DUAL_SYMBOLS) and not hasattr(lib, name):
             continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -524,6 +531,20 @@ class Engine:
         self._check(self.lib.wbc_device_outputs(self.h, *[C.byref(p) for p in ptrs]), "wbc_device_outputs")
         return dict(zip(("tau", "grf", "x", "status", "iters"), (p.value for p in ptrs)))
 
+    def duals(self) -> np.ndarray:
+        """wbc_get_duals: (B, 40) multipliers of the friction faces (rows 4 leg + face) and torque limits
+        (rows 16 + 2 joint + side) after step(... | DUALS); 0 for a row that does not bind, all 0 where
+        status is not QP_OK.  dual_rows() reshapes them."""
+        d = np.zeros((self.batch, DUAL_LEN))
+        self._check(self.lib.wbc_get_duals(self.h, _ptr(d)), "wbc_get_duals")
+        return d
+
+    def device_duals(self) -> int:
+        """wbc_device_duals: the device address of the (B, 40) multipliers."""
+        p = C.c_void_p()
+        self._check(self.lib.wbc_device_duals(self.h, C.byref(p)), "wbc_device_duals")
+        return p.value
+
     def objective(self) -> np.ndarray:
         """wbc_get_objective: (B,) QP objective of each hypothesis after step_modes(... | OBJECTIVE), row
         s * K + k as the other outputs; +inf where status is not QP_OK."""
@@ -555,6 +576,17 @@ class Engine:
         out = np.zeros((self.batch, DBG["LEN"]))
         self._check(self.lib.wbc_get_debug(self.h, _ptr(out)), "wbc_get_debug")
         return out
+
+
+def dual_rows(d):
+    """The (B, 40) multipliers of Engine.duals() by constraint: {"friction": (B, 4, 4) >= 0, leg by face in
+    the reference's order; "torque": (B, 12) signed, side 0 - side 1: positive where joint j sits at
+    -max_torque, negative at +max_torque (qpOASES' sign of the two-sided row's multiplier)}."""
+    d = np.asarray(d, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != DUAL_LEN:
+        raise ValueError(f"duals: need shape (B, {DUAL_LEN}), got {d.shape}")
+    t = d[:, 16:].reshape(-1, NUM_JOINTS, 2)
+    return {"friction": d[:, :16].reshape(-1, 4, 4).copy(), "torque": t[:, :, 0] - t[:, :, 1]}
 
 
 def split_debug(rec):

@@ -40,6 +40,10 @@ extern "C" hipError_t wbc_launch_modes_obj(const wbc::KernelArgs* a, hipStream_t
 extern "C" hipError_t wbc_launch_best_modes(const double* obj, const int32_t* status, const double* tau, const double* grf,
                                             int states, int modes, int32_t* best, double* bobj, double* btau, double* bgrf,
                                             hipStream_t st);
+// the default step's duals instances (wbc_kernel_du0.hip stateless, wbc_kernel_du1.hip stateful: wbc_step
+// with WBC_DUALS), declared here and not in wbc_layout.h's lists: a flag picks them, not the tables in force
+extern "C" hipError_t wbc_launch_update_solve_du0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_du1(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
 extern "C" hipError_t wbc_preload_resident();
@@ -131,6 +135,13 @@ struct wbc_engine {
     double* d_best_tau = nullptr;
     double* d_best_grf = nullptr;
     uint32_t modes_flags = 0;
+    // wbc_step with WBC_DUALS: the multipliers [B][WBC_DUAL_LEN], allocated at the first step that carries
+    // the flag; step_duals: the last wbc_step carried it.  Its kernels are base-body instances, so without
+    // a base-body table in force their step reads d_bb_def: base_row in B rows (built at the first use),
+    // and d_cn_flat / d_rp_uni as the base-body kernels do
+    double* d_dual = nullptr;
+    double* d_bb_def = nullptr;
+    bool step_duals = false;
     // bound (possibly external) inputs
     wbc::ConstInputView in{};
     // state / outputs
@@ -231,6 +242,7 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.mloop = 0;
     std::memset(a.mode_order, 0, sizeof(a.mode_order));
     a.obj = nullptr;
+    a.dual = nullptr;
     return a;
 }
 wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags) { return make_args(h, flags, h->in, h->out); }
@@ -441,6 +453,11 @@ int32_t refuse_mode_out_flags(const char* call, uint32_t flags) {
     if (!(flags & kModeOutFlags)) return WBC_OK;
     return fail(WBC_ERR_ARG, std::string(call) + ": WBC_OBJECTIVE / WBC_BEST are wbc_step_modes flags");
 }
+// WBC_DUALS belongs to wbc_step's default form; every other call refuses it
+int32_t refuse_duals_flag(const char* call, uint32_t flags) {
+    if (!(flags & WBC_DUALS)) return WBC_OK;
+    return fail(WBC_ERR_ARG, std::string(call) + ": WBC_DUALS is a flag of the default wbc_step");
+}
 }  // namespace
 
 extern "C" {
@@ -582,7 +599,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
-                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf};
+                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -850,6 +867,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_update: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_update", flags, 0, "default wbc_step only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_update", flags)) return rc;
+    if (const int32_t rc = refuse_duals_flag("wbc_update", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -864,6 +882,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_solve: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_solve", flags, 0, "default wbc_step only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_solve", flags)) return rc;
+    if (const int32_t rc = refuse_duals_flag("wbc_solve", flags)) return rc;
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
@@ -878,8 +897,23 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_step", flags, WBC_SPLIT | WBC_FUSED, "default form only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_step", flags)) return rc;
+    const bool duals = (flags & WBC_DUALS) != 0;
+    if (duals && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
+        return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
+    h->step_duals = false;
+    if (duals) {  // the engine's own tables for the ones the caller has not set, and the buffer
+        if (const int32_t rc = ensure_rp_cn_uniform(h)) return rc;
+        if (const int32_t rc = ensure_uniform(h, &h->d_bb_def, h->base_row, WBC_BB_LEN, "d_bb_def")) return rc;
+    }
     WBC_HIP(hipSetDevice(h->device));
+    if (duals && !h->d_dual) WBC_HIP(dalloc(&h->d_dual, (size_t)h->batch * WBC_DUAL_LEN));
     wbc::KernelArgs a = make_args(h, flags, io.in, io.out);
+    if (duals) {
+        if (!a.rp) a.rp = h->d_rp_uni;
+        if (!a.cn) a.cn = h->d_cn_flat;
+        if (!a.bb) a.bb = h->d_bb_def;
+        a.dual = h->d_dual;
+    }
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
     if (timed) WBC_HIP(hipEventRecord(h->ev0, h->stream));
     if (flags & WBC_SPLIT) {
@@ -898,13 +932,19 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         // parameter table too (the caller's, or the engine's uniform one), and under a
         // base-body table, which reads normals and parameters too
         WBC_HIP(begin_step16(h, a, flags, io.qmap));
-        WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr)](&a, h->stream));
+        // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks
+        if (duals) {
+            WBC_HIP((a.stateful ? wbc_launch_update_solve_du1 : wbc_launch_update_solve_du0)(&a, h->stream));
+        } else {
+            WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr)](&a, h->stream));
+        }
     }
     if (timed) {
         WBC_HIP(hipEventRecord(h->ev1, h->stream));
         h->timed = true;
     }
     h->updated = false;
+    h->step_duals = duals;
     return WBC_OK;
 }
 
@@ -944,6 +984,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_tables(h, "wbc_step_modes", flags, 0, "default wbc_step only")) return rc;
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
+    if (const int32_t rc = refuse_duals_flag("wbc_step_modes", flags)) return rc;
     const uint32_t mode_out = (flags & WBC_BEST) ? kModeOutFlags : (flags & WBC_OBJECTIVE);  // WBC_BEST implies WBC_OBJECTIVE
     if (mode_out && (flags & WBC_SPLIT))
         return fail(WBC_ERR_ARG, "wbc_step_modes: WBC_OBJECTIVE / WBC_BEST belong to the default form (not WBC_SPLIT)");
@@ -1106,6 +1147,7 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (!base_pose || !nu || !qj || !ref || !contacts || !switching) return fail(WBC_ERR_ARG, "wbc_cycle: null input");
     if (const int32_t rc = refuse_tables(h, "wbc_cycle", flags, WBC_SPLIT | WBC_FUSED | WBC_RESIDENT, "plain cycle only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_cycle", flags)) return rc;
+    if (const int32_t rc = refuse_duals_flag("wbc_cycle", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     if (!h->h_in) {
@@ -1197,6 +1239,22 @@ int32_t wbc_get_debug(wbc_engine* h, double* out) {
     WBC_HIP(hipSetDevice(h->device));
     WBC_HIP(hipMemcpyAsync(out, h->d_dbg, (size_t)h->batch * WBC_DBG_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     WBC_HIP(hipStreamSynchronize(h->stream));
+    return WBC_OK;
+}
+
+int32_t wbc_get_duals(wbc_engine* h, double* dual) {
+    if (!h || !dual) return fail(WBC_ERR_ARG, "null argument");
+    if (!h->step_duals) return fail(WBC_ERR_STATE, "wbc_get_duals: the last wbc_step did not carry WBC_DUALS");
+    WBC_HIP(hipSetDevice(h->device));
+    WBC_HIP(hipMemcpyAsync(dual, h->d_dual, (size_t)h->batch * WBC_DUAL_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));
+    return WBC_OK;
+}
+
+int32_t wbc_device_duals(wbc_engine* h, double** d_dual) {
+    if (!h || !d_dual) return fail(WBC_ERR_ARG, "null argument");
+    if (!h->step_duals) return fail(WBC_ERR_STATE, "wbc_device_duals: the last wbc_step did not carry WBC_DUALS");
+    *d_dual = h->d_dual;
     return WBC_OK;
 }
 

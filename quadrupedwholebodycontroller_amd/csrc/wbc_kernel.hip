@@ -5,6 +5,8 @@
 // step each, wbc_update_solve_kernel<STF, SONLY, RP, CN, BB>: stance, step0, step1 the plain ones
 // (stance-only, stateless, stateful), rps, rp0, rp1 the same under a per-robot parameter table (15),
 // cns, cn0, cn1 under per-robot contact normals (16), bbs, bb0, bb1 under a per-robot base body (18).
+// Two more, du0 and du1, hold bb0's and bb1's configuration under the kernel name wbc_update_solve_duals_kernel
+// (WBC_STEP_DUALS), whose solves also write the QP multipliers of the friction and torque rows (20).
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -1765,7 +1767,12 @@ __device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]
 // OBJ (the mode loop's objective instance, wbc_kernel_modes_obj.hip): the output stage also forms the
 // QP's objective at the optimum, 1/2 x^T H x + g^T x in its closed form, from the x it
 // forms whether or not KernelArgs::x is bound, and stores it to KernelArgs::obj (+infinity unless OK)
-template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false>
+// DU (the duals instances, wbc_kernel_du0.hip / wbc_kernel_du1.hip): the output stage also stores the
+// multiplier of every friction face and torque row to KernelArgs::dual: slot k < q of the
+// final working set holds its row id (act) and multiplier (u) in lane k; lane l owns rows l, 16 + l and
+// (l < 8) 32 + l, finds their slots by shuffling act and u over the twelve slots and writes each of its
+// rows once: the slot's u, 0 for a row outside the working set, 0 unless the status is OK
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false, bool DU = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
                         double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr) {
@@ -2028,6 +2035,12 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     x = xd;
                     ab = abd;
                     done = true;  // optimal: no row to add (iters 0, status OK)
+                    if constexpr (DU) {
+                        // the accepted point's rows as slots 0, 1 (ctz order, as the re-adds below leave
+                        // them): the segment is done, so only the output stage reads act and u
+                        if (l == 0) { act = pa; u = fmax(la, 0.0); }
+                        if (nw == 2 && l == 1) { act = pb; u = fmax(lb, 0.0); }
+                    }
                 } else if (!warm_pt) {
                     sp0 = t0s; sp1 = t1s; sp2 = t2s;
                 }
@@ -2429,6 +2442,24 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
         a.status[qp] = status;
         a.iters[qp] = iters;
     }
+    if constexpr (DU) {
+        // the multipliers by row (wbc.h WBC_DUAL_LEN): an inactive slot holds act = -1, which is no row's id
+        double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const int ak = seg_shfl_i(act, k);
+            const double uk = seg_shfl(u, k);
+            m0 = (ak == l) ? uk : m0;
+            m1 = (ak == 16 + l) ? uk : m1;
+            m2 = (ak == 32 + l) ? uk : m2;
+        }
+        if (wr) {
+            double* dr = a.dual + (size_t)qp * WBC_DUAL_LEN;
+            dr[l] = ok ? m0 : 0.0;
+            dr[16 + l] = ok ? m1 : 0.0;
+            if (l < 8) dr[32 + l] = ok ? m2 : 0.0;
+        }
+    }
     if (GEN && (STF < 0 ? a.stateful != 0 : STF == 1) && wr) {  // working set for the next cycle's hotstart, this numbering
         const unsigned long long b0 = __ballot((ab & 1) != 0), b1 = __ballot((ab & 2) != 0), b2 = __ballot((ab & 4) != 0);
         const int sh = (int)threadIdx.x & 48;
@@ -2487,7 +2518,7 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false>
+          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
@@ -3341,7 +3372,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             double hrow[12], gsv = 0.0;
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
-                solve16<true, false, STF, RP, CN>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf);
+                solve16<true, false, STF, RP, CN, false, DU>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf);
                 return true;
             }
             return false;
@@ -3351,8 +3382,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         bool vac = false;
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
-            solve16<true, true, STF, RP, CN>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK, hWlo, hWhi,
-                                             hWtag, cnf);
+            solve16<true, true, STF, RP, CN, false, DU>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
+                                                        hWlo, hWhi, hWtag, cnf);
             return true;
         }
         return false;
@@ -3708,7 +3739,8 @@ static_assert(offsetof(Presolve, presolved) == PRE_FLAG * sizeof(double), "PRE_F
 static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing");
 
 // OBJ: as solve16's (the objective from the recovered 42-vector, one entry per lane)
-template <bool CN = false, bool OBJ = false>
+// DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot)
+template <bool CN = false, bool OBJ = false, bool DU = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
@@ -4261,6 +4293,20 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
         a.status[rb] = status;
         a.iters[rb] = iters;
     }
+    if constexpr (DU) {
+        // row r = lane of wbc.h's 40 in this numbering (build_normal): friction face r of a stance leg is
+        // constraint neq + 4 (the leg's rank among the stance legs) + r % 4, torque row r constraint
+        // neq + nfr + r - 16; a swing leg's faces, the equalities and the swing slack rows have no row.
+        // The slot holding it carries its multiplier (slots >= q hold act = -1)
+        const int lg = (lane >> 2) & 3;
+        const int rank = __builtin_popcount(kap & ((1 << lg) - 1));
+        const int mine = (lane < 16) ? (((kap >> lg) & 1) ? mp.neq + 4 * rank + (lane & 3) : -2)
+                       : (lane < WBC_DUAL_LEN) ? mp.neq + mp.nfr + lane - 16 : -2;
+        double mv = 0.0;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) mv = (bcast_i(act, k) == mine) ? bcast(u, k) : mv;
+        if (lane < WBC_DUAL_LEN) a.dual[(size_t)rb * WBC_DUAL_LEN + lane] = ok ? mv : 0.0;
+    }
     if (Hh) {  // working set for the next cycle's hotstart
         const unsigned long long am = __ballot(is_con && !is_eq && active);
         if (lane == 0) {
@@ -4764,7 +4810,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
-template <bool CN = false, bool OBJ = false>
+template <bool CN = false, bool OBJ = false, bool DU = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -4773,11 +4819,12 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
+constexpr bool fb_writes_dual(int tag) { return tag >= FB_STEP_DU; }  // the duals instances (KernelArgs::dual), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
 __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base, const double* r, bool bad) {
@@ -4812,7 +4859,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
-        solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG), fb_writes_dual(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -4836,10 +4883,23 @@ __device__ __forceinline__ int xcd_block(int b, int n) {
 // wbc_kernel_bbs.hip): lane k < 14 of a segment loads entry k of row qp of KernelArgs::bb, indexed as
 // the other rows are, into the segment's 14 doubles of LDS beside UpdLds (448 B per workgroup); the
 // update reads its base body there (update_phase's bbr).
+// WBC_STEP_DUALS (wbc_kernel_du0.hip, wbc_kernel_du1.hip): the base-body instances' code under a kernel
+// name of its own, wbc_update_solve_duals_kernel (the macro below renames the kernel in those two units,
+// here and in the launcher; two units that instantiated one kernel symbol with different bodies would be
+// merged by the linker), whose solves also write the multipliers of the friction and torque rows
+// (solve16's DU; a fallback callee of its own, FB_STEP_DU); the engine runs it for a wbc_step that carries
+// WBC_DUALS, with all three tables bound (its own where the caller has none).
+#ifdef WBC_STEP_DUALS
+#define wbc_update_solve_kernel wbc_update_solve_duals_kernel
+constexpr bool STEP_DU = true;
+#else
+constexpr bool STEP_DU = false;
+#endif
 template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
+    static_assert(!STEP_DU || (BB && !SONLY), "the duals instances are base-body instances of any mask mix");
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
     const int K = a.modes;
@@ -4966,7 +5026,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
                 if (bbad) vin[0] = __builtin_nan("");
                 if (bbad) bbr = &L.model.base_mass;
             }
-            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB>(
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU>(
                 ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr);
         } else
         solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true>(ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg],
@@ -4992,7 +5052,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -5166,7 +5226,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
-template <bool CN, bool OBJ>
+template <bool CN, bool OBJ, bool DU>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -5193,7 +5253,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
-template <bool CN, bool OBJ>
+template <bool CN, bool OBJ, bool DU>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -5220,7 +5280,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase<CN, OBJ>(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN, OBJ, DU>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5475,6 +5535,7 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 extern "C" hipError_t WBC_STEP_LAUNCHER(const wbc::KernelArgs* a, hipStream_t st) {
     static_assert(wbc::UPD_RPW == wbc::QMAP_SEG, "the wave map's segments are the kernel's");
     if (wbc::step_args_refused(WBC_STEP_INSTANCE, *a)) return hipErrorInvalidValue;
+    if (wbc::STEP_DU && !a->dual) return hipErrorInvalidValue;
     hipLaunchKernelGGL((wbc::wbc_update_solve_kernel<WBC_STEP_INSTANCE>), dim3(a->nwaves), dim3(64), 0, st, *a);
     return hipGetLastError();
 }

@@ -1,0 +1,203 @@
+"""CPU: the QP multipliers of the default step (wbc_step with WBC_DUALS).
+
+  * the certificate of tests/duals_oracle.py on the numpy oracle's own x with least-squares multipliers: the
+    stationarity residual per input set, held against the committed record profiles/duals/oracle_residuals.json
+    (what the GPU test's bound is set from);
+  * the certificate has teeth: without the friction and torque multipliers, or with one of them off by 1e-6,
+    it fails;
+  * the GPU test's input sets have what it needs so that it cannot pass with nothing active;
+  * the boundary: dual_rows, constants, symbols, and the compiler's resource report of the two new kernel units.
+"""
+import os
+import re
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import duals_oracle as D
+import wbc_np as W
+from quadrupedwholebodycontroller_amd import _capi, dual_rows
+from test_robot_params_cpu import _report
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The oracle's own residual: an fp64 least-squares fit of at most 12 + 18 multipliers to 42 equations whose
+# entries reach 1e2-1e4 beside a gradient normalised to O(1): a few hundred ulps.  1e-11 is 50 x the worst
+# measured (2.0e-13) and far below the 1e-2 that a missing multiplier leaves.
+ORACLE_BOUND = 1e-11
+ISSUE_SETS = ("stress51_80Nm", "stress52_20Nm", "stress53_6Nm", "rl_random_48", "stance_cold_16", D.TABLES_SET)
+
+
+def active_rows(c):
+    """(friction, torque) rows of the 40 that are active at the oracle's x: a non-zero row of A (a swing leg's faces
+    are zero rows) tight at its bound by the 1e-7 (1 + |Ax|) test of wbc_np.kkt_residuals."""
+    H, g, A, lb, ub = c.qp
+    Ax = A @ c.qp_solution
+    tol = 1e-7 * (1.0 + np.abs(Ax))
+    nz = np.any(A != 0.0, axis=1)
+    fr = np.nonzero((nz & (np.abs(Ax - ub) <= tol))[18:34])[0]
+    lo, hi = (np.abs(Ax - lb) <= tol)[34:46], (np.abs(Ax - ub) <= tol)[34:46]
+    return fr, np.sort(np.concatenate([16 + 2 * np.nonzero(lo)[0], 17 + 2 * np.nonzero(hi)[0]]))
+
+
+# 1 ----------------------------------------------------------------------------------------------
+def test_certificate_on_the_oracles_own_x():
+    """Six input sets (and the GPU test's further ones): primal feasible, stationary to rounding, complementary at
+    the oracle's own activity threshold; the worst stationarity residual per set is the committed record's, to
+    the digits a libm or BLAS may move.  (No sign check here: where the tight rows are dependent, a leg with
+    zero force under all four of its faces, the least-squares multipliers are one solution of many and may be
+    negative; the engine's come from a working set of independent rows, and the GPU test checks their signs.)"""
+    both, recs = D.measure(), {k: D.record(k) for k in D.KINDS}
+    got, rec = both["stationarity"], recs["stationarity"]
+    assert set(ISSUE_SETS) <= set(got) and all(sorted(both[k]) == sorted(recs[k]) for k in D.KINDS)
+    for name, cs in [(n, D.cold_set(n)[2]) for n in (*D.COLD_SETS, D.TABLES_SET)] + [(D.TROT_SET, [c for row in D.trot_set()[1] for c in row])]:
+        n_ok = 0
+        for c in cs:
+            if c.qp_status != W.QP_OK:
+                continue
+            n_ok += 1
+            x = c.qp_solution
+            d = D.lsq_duals(c, x)
+            viol, stat, sign, comp = D.certificate(c, x, d)
+            assert viol <= 1e-7 * (1.0 + np.abs(c.qp[2] @ x).max()), (name, viol)
+            assert stat <= ORACLE_BOUND, (name, stat)
+            assert comp <= 1e-7, (name, comp)
+        assert n_ok > 0, name
+        print(f"oracle residual {name}: {got[name]:.2e} (record {rec[name]:.2e}), {n_ok} of {len(cs)} OK")
+        assert got[name] <= ORACLE_BOUND and rec[name] <= ORACLE_BOUND
+        assert 0.01 < (got[name] + 1e-16) / (rec[name] + 1e-16) < 100, (name, got[name], rec[name])
+        # the oracle's absolute primal violation: rounding of rows whose terms reach 1e3 (a few ulps of 1e3 is
+        # 1e-12); not zero, and above the relative stationarity figure on every set
+        pv, pr = both["primal"][name], recs["primal"][name]
+        print(f"oracle primal violation {name}: {pv:.2e} (record {pr:.2e})")
+        assert 0.0 < pv <= 1e-10 and 0.0 < pr <= 1e-10 and 0.01 < pv / pr < 100, (name, pv, pr)
+
+
+# 2 ----------------------------------------------------------------------------------------------
+def test_the_certificate_has_teeth():
+    """The 16-robot tables set.  Without the friction and torque multipliers the residual is above 1e-2 on every
+    robot that has an active row (15 of 16; measured 0.10 .. 0.93); one active multiplier scaled by 1 + 1e-6
+    puts the residual above the GPU test's bound of this set."""
+    _, _, cs = D.cold_set(D.TABLES_SET)
+    bound = D.gpu_bound(D.TABLES_SET)
+    n_active, dropped, scaled = 0, [], []
+    for b, c in enumerate(cs):
+        assert c.qp_status == W.QP_OK, b
+        x = c.qp_solution
+        d = D.lsq_duals(c, x)
+        assert D.certificate(c, x, d)[1] <= bound, b
+        if not d.any():
+            continue
+        n_active += 1
+        dropped.append(D.certificate(c, x, np.zeros(40))[1])
+        assert dropped[-1] > 1e-2, (b, dropped[-1])
+        d2 = d.copy()
+        d2[np.argmax(d)] *= 1.0 + 1e-6
+        scaled.append(D.certificate(c, x, d2)[1])
+        assert scaled[-1] > bound, (b, scaled[-1], bound)
+    print(f"{n_active} robots with an active row; multipliers dropped: residual {min(dropped):.2f} .. {max(dropped):.2f}; "
+          f"one scaled by 1 + 1e-6: {min(scaled):.1e} .. {max(scaled):.1e} (bound {bound:.1e})")
+    assert n_active == 15
+
+
+# 3 ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,n_ok,n_fr,n_tq", [("stress52_20Nm", 48, 38, 48), ("stress53_6Nm", 47, 38, 47),
+                                                 ("rl_random_48", None, 35, 44), ("stance_cold_16", None, 13, 0)])
+def test_gpu_sets_have_active_rows(name, n_ok, n_fr, n_tq):
+    """Robots OK, robots with an active friction row and with an active torque row, as measured; the 6 N m set
+    holds at least one robot that is not OK (whose 40 entries must be zero)."""
+    _, _, cs = D.cold_set(name)
+    ok = [c for c in cs if c.qp_status == W.QP_OK]
+    rows = [active_rows(c) for c in ok]
+    fr, tq = sum(len(f) > 0 for f, _ in rows), sum(len(t) > 0 for _, t in rows)
+    print(name, len(ok), "OK of", len(cs), "; active friction", fr, "torque", tq)
+    if n_ok is not None:
+        assert len(ok) == n_ok
+    if name == "stress53_6Nm":
+        assert len(ok) < len(cs)
+    assert (fr, tq) == (n_fr, n_tq)
+
+
+def test_further_gpu_sets_have_active_rows():
+    """The sets the GPU test adds: B = 45, the stretched legs (robots 0 and 15, whose stretched leg is a stance leg, take the fallback), the trot
+    at 40 N m (torque rows bind on most cycles)."""
+    for name in ("rl_random_45", "straight_20"):
+        cs = [c for c in D.cold_set(name)[2] if c.qp_status == W.QP_OK]
+        rows = [active_rows(c) for c in cs]
+        assert sum(len(f) + len(t) > 0 for f, t in rows) >= len(cs) // 2, name
+    cs = D.cold_set("straight_20")[2]
+    assert any(len(np.concatenate(active_rows(cs[b]))) for b in range(0, 20, 5) if cs[b].qp_status == W.QP_OK)
+    flat = [c for row in D.trot_set()[1] for c in row]
+    assert all(c.qp_status == W.QP_OK for c in flat)
+    n = sum(len(active_rows(c)[1]) > 0 for c in flat)
+    print("trot: robot-cycles with an active torque row", n, "of", len(flat))
+    assert n >= len(flat) // 2
+
+
+# 4 ----------------------------------------------------------------------------------------------
+def test_dual_rows_shapes_and_signs():
+    B = 3
+    d = np.zeros((B, 40))
+    d[0, 4 * 2 + 1] = 2.0      # leg 2, face 1
+    d[1, 16 + 2 * 5] = 3.0     # joint 5 at -max_torque
+    d[2, 16 + 2 * 11 + 1] = 4.0  # joint 11 at +max_torque
+    r = dual_rows(d)
+    assert r["friction"].shape == (B, 4, 4) and r["torque"].shape == (B, 12)
+    assert r["friction"][0, 2, 1] == 2.0 and r["friction"].sum() == 2.0 and (r["friction"] >= 0).all()
+    assert r["torque"][1, 5] == 3.0 and r["torque"][2, 11] == -4.0 and np.abs(r["torque"]).sum() == 7.0
+    # the signed torque entry is qpOASES' multiplier of the two-sided row
+    _, _, cs = D.cold_set(D.TABLES_SET)
+    for c in cs:
+        d1 = D.lsq_duals(c, c.qp_solution)
+        y = D.expand(c, c.qp_solution, d1)
+        rr = dual_rows(d1[None])
+        assert np.array_equal(rr["torque"][0], y[34:46]) and np.array_equal(rr["friction"][0].ravel(), -y[18:34])
+    for bad in (np.zeros(40), np.zeros((2, 39)), np.zeros((2, 4, 10))):
+        with pytest.raises(ValueError, match="need shape"):
+            dual_rows(bad)
+
+
+def test_names_follow_the_header():
+    hdr = open(os.path.join(ROOT, "include", "wbc.h")).read()
+    assert int(re.search(r"#define WBC_DUALS (\d+)u", hdr).group(1)) == _capi.DUALS == 2048
+    assert int(re.search(r"WBC_DUAL_LEN = (\d+)", hdr).group(1)) == _capi.DUAL_LEN == D.DUAL_LEN == 40
+    flags = [int(v) for v in re.findall(r"#define WBC_[A-Z_]+ (\d+)u", hdr)]
+    assert len(set(flags)) == len(flags) and all(f & (f - 1) == 0 for f in flags)  # one bit each, none shared
+    for s in ("wbc_get_duals", "wbc_device_duals"):
+        assert s in _capi.C_API_SYMBOLS and s in _capi.DUAL_SYMBOLS and re.search(rf"int32_t {s}\(", hdr)
+    lay = open(os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc", "wbc_layout.h")).read()
+    body = lay[lay.index("struct KernelArgs {"):]
+    body = body[:body.index("\n};")]
+    decl = [l.split("//")[0].strip() for l in body.split("\n") if l.split("//")[0].strip().endswith(";")]
+    assert decl[-1] == "double* dual;" and decl[-2] == "double* obj;"  # KernelArgs::dual is last: no other offset moves
+
+
+# 5 ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("unit,var,kernel,base,base_var", [
+    ("du0", "DU0_KFLAGS", "wbc_update_solve_duals_kernelILi0ELb0ELb1ELb1ELb1E", "bb0", "BB0_KFLAGS"),
+    ("du1", "DU1_KFLAGS", "wbc_update_solve_duals_kernelILi1ELb0ELb1ELb1ELb1E", "bb1", "BB1_KFLAGS"),
+])
+def test_new_units_resources(unit, var, kernel, base, base_var):
+    """The duals instances keep the base-body instances' footprint: at most 256 VGPRs, no more LDS than the
+    bb unit's 40 720 B (four workgroups per CU), one wave per SIMD, no scratch instruction in the kernel's own
+    body, the unit holding the kernel and one drain_fallbacks only; and under the bb unit's scheduler flags."""
+    mk = open(os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc", "Makefile")).read()
+    flags = lambda v: re.search(rf"^{v} := (.*)$", mk, re.M).group(1).split()
+    assert flags(var) == flags(base_var)
+    with ThreadPoolExecutor(2) as ex:
+        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+    assert len(new) == 1 and len(old) == 1, (list(new), list(old))
+    (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
+    assert kernel in name, name
+    print(unit, rep, "against", base, ref)
+    assert rep["VGPRs"] <= 256, rep
+    assert rep["LDS Size [bytes/block]"] <= ref["LDS Size [bytes/block]"] == 40720, (rep, ref)
+    assert rep["Occupancy [waves/SIMD]"] == ref["Occupancy [waves/SIMD]"] == 1, (rep, ref)
+    lines = asm.split("\n")
+    starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]
+    ends = [i for i, l in enumerate(lines) if l.startswith(".Lfunc_end")]
+    assert len(starts) == 2 and sum("drain_fallbacks" in n for _, n in starts) == 1, [n for _, n in starts]
+    for i, n in starts:
+        if "drain_fallbacks" not in n:
+            body = lines[i:min(x for x in ends if x > i)]
+            assert not [l for l in body if "scratch_" in l], n
