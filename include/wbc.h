@@ -432,6 +432,50 @@ int32_t wbc_bind_device_base_body(wbc_engine* h, const double* d_table);
  * every row.  Column 13 is written as 0. */
 int32_t wbc_get_base_body(wbc_engine* h, double* table);
 
+/* Per-robot joint torque bounds and per-foot friction coefficients (actuator limits that differ per
+ * joint, are asymmetric and change every cycle with the torque-speed envelope; a derated or dead
+ * actuator; feet on different ground): a table of doubles, row-major [B][WBC_LM_LEN], row b for robot
+ * b.  Rows are 224 bytes, so a table that starts 16-byte aligned keeps every row 16-byte aligned
+ * (required of a device-bound table).  While a limits table is in force the torque rows of robot b's
+ * QP are, per joint j,
+ *     tau_j >= tau_min[j]  (side 0)      tau_j <= tau_max[j]  (side 1)
+ * in the row numbering of WBC_DUALS, and the friction faces of foot l use mu[l] (on that foot's own
+ * frame under contact normals).  The friction and max_torque columns of a parameter table, and of
+ * wbc_params, are then not read for that robot's rows; the gains and the slack weight still come from
+ * them.  The row (-max_torque x 12, +max_torque x 12, friction x 4), which wbc_get_limits returns
+ * without a table, gives the step without a limits table bit for bit.  A row is valid when its 28
+ * entries are finite, tau_min[j] <= tau_max[j] (equal: a dead or locked-torque actuator) and
+ * mu[l] >= 0.  A bound is a finite number: an unbounded joint is a large one. */
+enum {
+    WBC_LM_TAU_MIN = 0,   /* [12] lower torque bound per joint, N m (joint order of tau) */
+    WBC_LM_TAU_MAX = 12,  /* [12] upper torque bound per joint */
+    WBC_LM_FRICTION = 24, /* [4]  mu per foot (LH, LF, RF, RH) */
+    WBC_LM_LEN = 28
+};
+/* Host table, validated and then copied on the engine stream (the call synchronizes it, so the
+ * caller may reuse the array).  An invalid row returns WBC_ERR_ARG, wbc_last_error names the row and
+ * the column, and the table in force before the call stays in force.  NULL clears the table: back
+ * to max_torque and friction.
+ * While a limits table is in force (this one or a device-bound one), with or without the other
+ * three tables:
+ *  - supported: wbc_step in its default form (stateless, stateful and WBC_COLD; with WBC_DEBUG,
+ *    WBC_NO_X, WBC_TIMED, WBC_GROUP and WBC_DUALS) and plain wbc_cycle.  A row may change between
+ *    stateful cycles: the hotstart's own check rejects a warm set that no longer fits.
+ *  - refused with WBC_ERR_STATE (wbc_last_error names the call or flag): wbc_update, wbc_solve,
+ *    wbc_step_modes, and wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT.  These
+ *    forms read max_torque and friction only; they run as before once the table is cleared
+ *    (wbc_set_limits(h, NULL) and no device table bound). */
+int32_t wbc_set_limits(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_LM_LEN] (no copy, no host validation; the step reads the pointer
+ * directly, so a caller may rewrite it on the engine's stream every cycle).  NULL restores the
+ * engine-owned table of wbc_set_limits, or none if none was set.  On the device an invalid row gives
+ * that robot WBC_QP_NUMERIC and zero outputs, as a non-finite input does; no other robot is touched. */
+int32_t wbc_bind_device_limits(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_LM_LEN] to the host (synchronous); without one, every robot's
+ * (-max_torque x 12, +max_torque x 12, friction x 4), from its parameter row when a parameter table is
+ * in force, else from wbc_params. */
+int32_t wbc_get_limits(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

@@ -34,10 +34,15 @@ BB_LEN = 14
 BB_MASS, BB_COM, BB_INERTIA = 0, 1, 4
 BASE_BODY_NAMES = ("mass", "com", "inertia")
 BB_COLUMN_NAMES = ("mass", "com_x", "com_y", "com_z", "I_xx", "I_xy", "I_xz", "I_yx", "I_yy", "I_yz", "I_zx", "I_zy", "I_zz")
+# the per-robot limits table (WBC_LM_* in include/wbc.h): tau_min[12], tau_max[12] (joint order of tau), mu per
+# foot (LH, LF, RF, RH)
+LM_LEN = 28
+LM_TAU_MIN, LM_TAU_MAX, LM_FRICTION = 0, 12, 24
+LIMIT_NAMES = ("tau_min", "tau_max", "friction")
 
 # the per-robot tables of the default step: name -> row length; the C entry points of table <name> are
 # wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
-TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN}
+TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN, "limits": LM_LEN}
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
 # the objective and best-mode outputs of wbc_step_modes (WBC_OBJECTIVE / WBC_BEST)
 MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
@@ -329,6 +334,69 @@ def base_body_with_payload(model: WbcModel, mass, position, inertia=None) -> np.
     return out[0] if single else out
 
 
+def limits_row(tau_min, tau_max, friction) -> np.ndarray:
+    """One (LM_LEN,) row of the limits table: tau_min and tau_max a scalar or (12,) (joint order of tau),
+    friction a scalar or (4,) (feet LH, LF, RF, RH).  limits_row(-T, T, mu) is the row of a robot with
+    max_torque T and friction mu."""
+    row = np.empty(LM_LEN)
+    for name, v, at, n in (("tau_min", tau_min, LM_TAU_MIN, NUM_JOINTS), ("tau_max", tau_max, LM_TAU_MAX, NUM_JOINTS),
+                           ("friction", friction, LM_FRICTION, 4)):
+        v = np.asarray(v, np.float64)
+        if v.shape not in ((), (n,)):
+            raise ValueError(f"limits {name}: need a scalar or shape ({n},), got {v.shape}")
+        row[at:at + n] = v
+    return row
+
+
+def limits_bad_column(row) -> int:
+    """The validity rule of one limits row (wbc_layout.h lm_bad_column): -1, or the first failing column."""
+    r = np.asarray(row, np.float64)
+    for c in range(LM_LEN):
+        if not np.isfinite(r[c]):
+            return c
+        if LM_TAU_MAX <= c < LM_FRICTION and not r[c - LM_TAU_MAX + LM_TAU_MIN] <= r[c]:
+            return c
+        if c >= LM_FRICTION and r[c] < 0.0:
+            return c
+    return -1
+
+
+def limits_table(batch: int, defaults, table) -> np.ndarray:
+    """The [B, LM_LEN] table of wbc_set_limits from a (B, 28) array, one (28,) row broadcast to all robots,
+    or a dict of LIMIT_NAMES -> a scalar, one (12,) / (4,) vector, a (B,) value per robot or a (B, 12) /
+    (B, 4) array, whose missing entries take the rows of `defaults` ((B, 28): Engine.limits()).  Validated
+    as the engine validates it (finite, tau_min <= tau_max per joint, friction >= 0); ValueError names the
+    row and the column."""
+    B = int(batch)
+    out = np.array(np.broadcast_to(np.asarray(defaults, np.float64), (B, LM_LEN)))
+    if isinstance(table, dict):
+        unknown = sorted(set(table) - set(LIMIT_NAMES))
+        if unknown:
+            raise ValueError(f"unknown limits entries {unknown}; entries are {LIMIT_NAMES}")
+        for name, at, n in (("tau_min", LM_TAU_MIN, NUM_JOINTS), ("tau_max", LM_TAU_MAX, NUM_JOINTS), ("friction", LM_FRICTION, 4)):
+            if name not in table:
+                continue
+            v = np.asarray(table[name], np.float64)
+            if v.shape == (B,) and B != n:
+                v = v[:, None]
+            elif v.shape not in ((), (n,), (B, n)):
+                raise ValueError(f"limits {name}: need a scalar, shape ({n},), ({B},) or ({B}, {n}), got {v.shape}")
+            out[:, at:at + n] = v
+    else:
+        t = np.asarray(table, np.float64)
+        if t.shape not in ((LM_LEN,), (B, LM_LEN)):
+            raise ValueError(f"limits table: need shape ({B}, {LM_LEN}) or ({LM_LEN},), got {t.shape}")
+        out[:, :] = t
+    for b in range(B):
+        c = limits_bad_column(out[b])
+        if c >= 0:
+            name, k = (("tau_min", c) if c < LM_TAU_MAX else ("tau_max", c - LM_TAU_MAX) if c < LM_FRICTION
+                       else ("friction", c - LM_FRICTION))
+            raise ValueError(f"limits: row {b}, column {c} ({name}[{k}]) = {out[b, c]:g}: need finite entries, "
+                             "tau_min <= tau_max per joint, friction >= 0")
+    return np.ascontiguousarray(out)
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -455,6 +523,26 @@ class Engine:
     def base_body(self) -> np.ndarray:
         """wbc_get_base_body: the [B, 14] table in force (without one: the model's base in every row)."""
         return self._get_table("base_body")
+
+    def set_limits(self, table):
+        """wbc_set_limits: per-robot joint torque bounds [tau_min, tau_max] and per-foot friction for the
+        default step.  `table`: a (B, 28) array, one (28,) row (limits_row), or a dict {tau_min, tau_max,
+        friction} of scalars, (12,) / (4,) vectors or per-robot arrays (limits_table), whose missing entries
+        keep what limits() returns now; None clears the table: max_torque and friction again."""
+        self._set_table("limits", None if table is None else
+                        limits_table(self.batch, self.limits() if isinstance(table, dict) else 0.0, table))
+
+    def bind_device_limits(self, table=0):
+        """wbc_bind_device_limits: a caller-owned device table [B, 28] of doubles (no copy, no host
+        validation; it may be rewritten on the engine's stream every cycle): an integer device pointer, or
+        an object with data_ptr() (a torch tensor), which the engine keeps referenced while it is bound.
+        0 / None: the engine-owned table, or none."""
+        self._bind_table("limits", table)
+
+    def limits(self) -> np.ndarray:
+        """wbc_get_limits: the [B, 28] table in force (without one: -max_torque x 12, +max_torque x 12 and
+        friction x 4 per robot, from its parameter row or the engine-wide params)."""
+        return self._get_table("limits")
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

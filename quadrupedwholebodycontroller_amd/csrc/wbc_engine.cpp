@@ -25,15 +25,16 @@ extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStre
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st);
 // The default step's launchers (wbc_launch_update_solve_<unit> of wbc_kernel_<unit>.hip), indexed by
 // wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's; the base-body units'
-// (WBC_STEP_UNITS_BB) follow the nine
+// (WBC_STEP_UNITS_BB) follow the nine, the limits units' (WBC_STEP_UNITS_LM) those
 #define X(unit) extern "C" hipError_t wbc_launch_update_solve_##unit(const wbc::KernelArgs* a, hipStream_t st);
 WBC_STEP_UNITS(X)
 WBC_STEP_UNITS_BB(X)
+WBC_STEP_UNITS_LM(X)
 #undef X
 #define X(unit) wbc_launch_update_solve_##unit,
-static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X)};
+static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X) WBC_STEP_UNITS_LM(X)};
 #undef X
-static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_ALL_INSTANCES, "one launcher per instance");
+static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_EVERY_INSTANCE, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 // the mode loop's objective instance (wbc_kernel_modes_obj.hip) and the selection after it (WBC_BEST)
 extern "C" hipError_t wbc_launch_modes_obj(const wbc::KernelArgs* a, hipStream_t st);
@@ -44,6 +45,9 @@ extern "C" hipError_t wbc_launch_best_modes(const double* obj, const int32_t* st
 // with WBC_DUALS), declared here and not in wbc_layout.h's lists: a flag picks them, not the tables in force
 extern "C" hipError_t wbc_launch_update_solve_du0(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update_solve_du1(const wbc::KernelArgs* a, hipStream_t st);
+// and the limits units' duals instances (wbc_kernel_lmd0.hip, wbc_kernel_lmd1.hip: WBC_DUALS under a limits table)
+extern "C" hipError_t wbc_launch_update_solve_lmd0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_lmd1(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
 extern "C" hipError_t wbc_preload_resident();
@@ -142,6 +146,10 @@ struct wbc_engine {
     double* d_dual = nullptr;
     double* d_bb_def = nullptr;
     bool step_duals = false;
+    // per-robot torque bounds and per-foot friction (KernelArgs::lm, [B][WBC_LM_LEN]; without: -+max_torque
+    // and friction).  The kernels that read them are base-body instances, so without a base-body table in
+    // force their step reads d_bb_def, and d_cn_flat / d_rp_uni as the base-body kernels do
+    RobotTable lm{WBC_LM_LEN};
     // bound (possibly external) inputs
     wbc::ConstInputView in{};
     // state / outputs
@@ -210,9 +218,10 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force) ? h->d_rp_uni : nullptr);
-    a.cn = h->cn.in_force ? h->cn.in_force : (h->bb.in_force ? h->d_cn_flat : nullptr);
-    a.bb = h->bb.in_force;
+    a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force || h->lm.in_force) ? h->d_rp_uni : nullptr);
+    a.cn = h->cn.in_force ? h->cn.in_force : ((h->bb.in_force || h->lm.in_force) ? h->d_cn_flat : nullptr);
+    a.bb = h->bb.in_force ? h->bb.in_force : (h->lm.in_force ? h->d_bb_def : nullptr);
+    a.lm = h->lm.in_force;
     a.base_pose = in.pose;
     a.nu = in.nu;
     a.qj = in.qj;
@@ -428,8 +437,8 @@ hipError_t launch_solves(wbc_engine* h, wbc::KernelArgs& a) {
 
 // The per-robot tables are read by the default wbc_step (and the plain wbc_cycle) only: with one in
 // force `call` is refused, outright (forms = 0) or when `flags` ask for one of `forms`.  The
-// parameter table is named before the normals, the base bodies last; `allowed` says what the call may
-// still do.
+// parameter table is named before the normals, then the base bodies, the limits last; `allowed` says
+// what the call may still do.
 int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uint32_t forms, const char* allowed) {
     if (forms && !(flags & forms)) return WBC_OK;
     const char* form = !forms ? nullptr : (flags & WBC_SPLIT) ? "WBC_SPLIT" : (flags & WBC_FUSED) ? "WBC_FUSED" : "WBC_RESIDENT";
@@ -437,6 +446,7 @@ int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uin
         {&wbc_engine::rp, "a per-robot parameter table", " is in force", "it with wbc_set_robot_params"},
         {&wbc_engine::cn, "contact normals", " are in force", "them with wbc_set_contact_normals"},
         {&wbc_engine::bb, "a per-robot base body table", " is in force", "it with wbc_set_base_body"},
+        {&wbc_engine::lm, "per-robot limits", " are in force", "them with wbc_set_limits"},
     };
     for (const auto& t : kTables) {
         if (!(h->*t.table).in_force) continue;
@@ -599,7 +609,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
-                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def};
+                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -715,10 +725,17 @@ static int32_t ensure_rp_cn_uniform(wbc_engine* h) {
     return ensure_uniform(h, &h->d_cn_flat, kFlatNormals, WBC_CN_LEN, "d_cn_flat");
 }
 
+// and the model's base in B rows, which the limits kernels (and the duals kernels) read when no
+// base-body table is in force
+static int32_t ensure_rp_cn_bb_uniform(wbc_engine* h) {
+    if (const int32_t rc = ensure_rp_cn_uniform(h)) return rc;
+    return ensure_uniform(h, &h->d_bb_def, h->base_row, WBC_BB_LEN, "d_bb_def");
+}
+
 // The three calls of a per-robot table (RobotTable), for the parameters and for the normals.  What
 // differs is passed in: `call` (the C entry point, for messages), `what` (the own table's name in
 // allocation errors), row_error (why the host refuses row b, or "" for a row it accepts), uniform
-// (the table's kernels read other tables too: ensure_rp_uniform, ensure_rp_cn_uniform; or null) and,
+// (the table's kernels read other tables too: ensure_rp_uniform, ensure_rp_cn_uniform, ensure_rp_cn_bb_uniform; or null) and,
 // to read back without a table in force, the default rows.
 // Set from the host: a refused table leaves the previous one in force.
 static int32_t table_set(wbc_engine* h, RobotTable wbc_engine::*which, const double* table, const char* call,
@@ -797,6 +814,16 @@ static std::string bb_row_error(const double* row) {
     return "column " + std::to_string(c) + " (" + names[c] + ") = " + val +
            ": need finite entries, mass > 0 and a symmetric (to 1e-9 of its trace), positive definite inertia";
 }
+static std::string lm_row_error(const double* row) {
+    const int c = wbc::lm_bad_column(row);
+    if (c < 0) return "";
+    const char* group = c < WBC_LM_TAU_MAX ? "tau_min" : c < WBC_LM_FRICTION ? "tau_max" : "friction";
+    const int k = c < WBC_LM_TAU_MAX ? c : c < WBC_LM_FRICTION ? c - WBC_LM_TAU_MAX : c - WBC_LM_FRICTION;
+    char val[32];
+    std::snprintf(val, sizeof(val), "%g", row[c]);
+    return "column " + std::to_string(c) + " (" + group + "[" + std::to_string(k) + "]) = " + val +
+           ": need finite entries, tau_min <= tau_max per joint, friction >= 0";
+}
 static std::string cn_row_error(const double* row) {
     static const char* const feet[WBC_NUM_LEGS] = {"LH", "LF", "RF", "RH"};
     const int l = wbc::cn_bad_foot(row);
@@ -843,6 +870,32 @@ int32_t wbc_get_base_body(wbc_engine* h, double* table) {
     if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
     if (const int32_t rc = table_get(h, &wbc_engine::bb, table, h->base_row)) return rc;
     for (size_t b = 0; b < (size_t)h->batch; ++b) table[b * WBC_BB_LEN + WBC_BB_LEN - 1] = 0.0;  // the reserved column
+    return WBC_OK;
+}
+
+int32_t wbc_set_limits(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::lm, table, "wbc_set_limits", "d_lm", lm_row_error, ensure_rp_cn_bb_uniform);
+}
+int32_t wbc_bind_device_limits(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::lm, d_table, "wbc_bind_device_limits", ensure_rp_cn_bb_uniform);
+}
+// Without a limits table: each robot's -+max_torque and friction, from its parameter row when a
+// parameter table is in force, else from the engine-wide params
+int32_t wbc_get_limits(wbc_engine* h, double* table) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    if (h->lm.in_force) return table_get(h, &wbc_engine::lm, table, nullptr);
+    const size_t B = (size_t)h->batch;
+    std::vector<double> rp(B * WBC_RP_LEN);
+    if (const int32_t rc = wbc_get_robot_params(h, rp.data())) return rc;
+    for (size_t b = 0; b < B; ++b) {
+        double* row = table + b * WBC_LM_LEN;
+        const double T = rp[b * WBC_RP_LEN + WBC_RP_MAX_TORQUE], mu = rp[b * WBC_RP_LEN + WBC_RP_FRICTION];
+        for (int j = 0; j < WBC_NUM_JOINTS; ++j) {
+            row[WBC_LM_TAU_MIN + j] = -T;
+            row[WBC_LM_TAU_MAX + j] = T;
+        }
+        for (int l = 0; l < WBC_NUM_LEGS; ++l) row[WBC_LM_FRICTION + l] = mu;
+    }
     return WBC_OK;
 }
 
@@ -902,8 +955,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
     h->step_duals = false;
     if (duals) {  // the engine's own tables for the ones the caller has not set, and the buffer
-        if (const int32_t rc = ensure_rp_cn_uniform(h)) return rc;
-        if (const int32_t rc = ensure_uniform(h, &h->d_bb_def, h->base_row, WBC_BB_LEN, "d_bb_def")) return rc;
+        if (const int32_t rc = ensure_rp_cn_bb_uniform(h)) return rc;
     }
     WBC_HIP(hipSetDevice(h->device));
     if (duals && !h->d_dual) WBC_HIP(dalloc(&h->d_dual, (size_t)h->batch * WBC_DUAL_LEN));
@@ -930,13 +982,18 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         // (DESIGN.md 4.22), any other step the stateless or the stateful one; the same three under a
         // per-robot parameter table in force and under contact normals, which read the
         // parameter table too (the caller's, or the engine's uniform one), and under a
-        // base-body table, which reads normals and parameters too
+        // base-body table, which reads normals and parameters too; the stateless or the
+        // stateful one under a limits table, which reads all three
         WBC_HIP(begin_step16(h, a, flags, io.qmap));
-        // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks
-        if (duals) {
+        // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks; under
+        // a limits table the limits units' own
+        if (duals && a.lm) {
+            WBC_HIP((a.stateful ? wbc_launch_update_solve_lmd1 : wbc_launch_update_solve_lmd0)(&a, h->stream));
+        } else if (duals) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_du1 : wbc_launch_update_solve_du0)(&a, h->stream));
         } else {
-            WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr)](&a, h->stream));
+            WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr,
+                                                      a.lm != nullptr)](&a, h->stream));
         }
     }
     if (timed) {

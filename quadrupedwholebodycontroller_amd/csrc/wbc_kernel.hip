@@ -7,6 +7,8 @@
 // cns, cn0, cn1 under per-robot contact normals (16), bbs, bb0, bb1 under a per-robot base body (18).
 // Two more, du0 and du1, hold bb0's and bb1's configuration under the kernel name wbc_update_solve_duals_kernel
 // (WBC_STEP_DUALS), whose solves also write the QP multipliers of the friction and torque rows (20).
+// Four more hold the instances under per-robot torque bounds and per-foot friction, a sixth template
+// argument LM (21): lm0 and lm1, and lmd0 and lmd1, the same with WBC_STEP_DUALS.
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -1772,10 +1774,17 @@ __device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]
 // final working set holds its row id (act) and multiplier (u) in lane k; lane l owns rows l, 16 + l and
 // (l < 8) 32 + l, finds their slots by shuffling act and u over the twelve slots and writes each of its
 // rows once: the slot's u, 0 for a row outside the working set, 0 unless the status is OK
-template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false, bool DU = false>
+// LM (with CN; the limits instances, wbc_kernel_lm0.hip / wbc_kernel_lm1.hip, KernelArgs::lm):
+// lmv holds what the lane's own rows need of its robot's limits row: the bound of torque row 16 + l
+// (joint l >> 1: tau_min on side 0, tau_max on side 1), of row 32 + l (joint 8 + (l & 7 >> 1)) and the mu
+// of its face's leg; they stand in for -+max_torque and friction.  Another lane's row is never rebuilt
+// from its bound: its slack comes from the owner lane and, under CN, so does its face.
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
-                        double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr) {
+                        double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr,
+                        [[maybe_unused]] const double* lmv = nullptr) {
+    static_assert(!LM || CN, "the limits instances are contact-normal instances");
     constexpr int N = 12;
     constexpr int NTS = GEN ? 12 : NTS_ST;  // Nt row stride
     const wbc_params& pr = a.pv;
@@ -1802,11 +1811,14 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
         const double nt2 = V.Nt[k2 * NTS + m];  // (k2 is a valid row in every lane: loaded, then masked)
         n2[m] = v2 ? -sg * nt2 : 0.0;
     }
-    const double bp1 = -pr.max_torque - sg * V.t0[k1], bp2 = -pr.max_torque - sg * V.t0[k2];
+    // (LM: side 0 is tau_min - t0, side 1 t0 - tau_max; with -+max_torque the bits of the line below)
+    const double bp1 = LM ? sg * (lmv[0] - V.t0[k1]) : -pr.max_torque - sg * V.t0[k1];
+    const double bp2 = LM ? sg * (lmv[1] - V.t0[k2]) : -pr.max_torque - sg * V.t0[k2];
     const double tol0 = 1e-10;
-    const double tol1 = 1e-10 * fmax(1.0, fabs(-pr.max_torque - sg * P.bbj[k1]));
-    const double tol2 = 1e-10 * fmax(1.0, fabs(-pr.max_torque - sg * P.bbj[k2]));
-    const double in0 = fast_rsq(fmax(1.0 + pr.friction * pr.friction, 1e-300));
+    const double tol1 = 1e-10 * fmax(1.0, fabs(LM ? lmv[0] - P.bbj[k1] : -pr.max_torque - sg * P.bbj[k1]));
+    const double tol2 = 1e-10 * fmax(1.0, fabs(LM ? lmv[1] - P.bbj[k2] : -pr.max_torque - sg * P.bbj[k2]));
+    const double mu0 = LM ? lmv[2] : pr.friction;
+    const double in0 = fast_rsq(fmax(1.0 + mu0 * mu0, 1e-300));
     const double in1 = fast_rsq(fmax(V.nsel[k1], 1e-300)), in2 = fast_rsq(fmax(V.nsel[k2], 1e-300));
     double sp0, sp1, sp2;
     auto slacks = [&](const double* xv) {
@@ -2518,12 +2530,15 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false>
+          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false, bool LM = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
-                             [[maybe_unused]] const double* cnf = nullptr, [[maybe_unused]] const double* bbr = nullptr) {
+                             [[maybe_unused]] const double* cnf = nullptr, [[maybe_unused]] const double* bbr = nullptr,
+                             [[maybe_unused]] const double* lmv = nullptr) {
     const wbc_params& pr = a.pv;
+    // LM (the limits instances, KernelArgs::lm): lmv is the lane's share of its robot's limits row, handed
+    // on to solve16; the update itself reads neither bound nor mu
     // BB (the base-body instances, KernelArgs::bb): bbr is the robot's base body, 13 doubles laid out as
     // the model's first 13 (mass, com, inertia: a wbc.h WBC_BB_LEN row in LDS, or the model's own base
     // for a row the step does not accept); it stands in for md's base at the four places that read it
@@ -3372,7 +3387,7 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             double hrow[12], gsv = 0.0;
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
-                solve16<true, false, STF, RP, CN, false, DU>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf);
+                solve16<true, false, STF, RP, CN, false, DU, LM>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf, lmv);
                 return true;
             }
             return false;
@@ -3382,8 +3397,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         bool vac = false;
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
-            solve16<true, true, STF, RP, CN, false, DU>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
-                                                        hWlo, hWhi, hWtag, cnf);
+            solve16<true, true, STF, RP, CN, false, DU, LM>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
+                                                            hWlo, hWhi, hWtag, cnf, lmv);
             return true;
         }
         return false;
@@ -3464,10 +3479,12 @@ __device__ __forceinline__ int nth_leg(int kap, int idx, int want) {
 //   R4/R5 swing rows      +-(Js_j qdd + Js_com a) + s >= +-c'                     (cpp:496-497,507-515)
 // CN: cn is the QP's row of KernelArgs::cn, and a friction face stands on its foot's own frame
 // (cn_frame; a foot the step does not accept stands on flat ground: its robot is flagged)
-template <bool CN = false>
+// LM: lm is the QP's row of KernelArgs::lm (null for a row the step does not accept: its robot is flagged
+// and pr's values stand): torque row (j, side) takes tau_min[j] / tau_max[j], a face of leg l mu[l]
+template <bool CN = false, bool LM = false>
 __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& mp, const wbc_params& pr, int p,
                              double* n, double& b, bool& is_eq, double& nsel, double& tolv,
-                             [[maybe_unused]] const double* cn = nullptr) {
+                             [[maybe_unused]] const double* cn = nullptr, [[maybe_unused]] const double* lm = nullptr) {
     const int kap = mp.kap;
     const int t_fr = mp.neq, t_tq = mp.neq + mp.nfr, t_sw = t_tq + mp.ntq;
     const bool in = p < mp.m;
@@ -3493,6 +3510,8 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
     const double scp = eq ? 1.0 : (sw ? sg : 0.0);
     const double stq = tq ? -sg : 0.0;
     const double* grow = G[3 * l + k];
+    [[maybe_unused]] double mul = 0.0;  // LM: the leg's mu
+    if constexpr (LM) mul = lm ? lm[WBC_LM_FRICTION + l] : pr.friction;
     [[maybe_unused]] double cnn[3], ct1[3], ct2[3];
     if constexpr (CN) {
         const double cm[3] = {cn[3 * l], cn[3 * l + 1], cn[3 * l + 2]};
@@ -3509,7 +3528,7 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
             const double fv = (r == 0) ? ((rr == 0) ? -1.0 : (rr == 1 ? 1.0 : 0.0))
                             : (r == 1) ? ((rr == 2) ? -1.0 : (rr == 3 ? 1.0 : 0.0)) : pr.friction;
             if constexpr (CN) {
-                if (fr && mm == l) x = cn_face_elem(cnn, ct1, ct2, pr.friction, rr, r);
+                if (fr && mm == l) x = cn_face_elem(cnn, ct1, ct2, LM ? mul : pr.friction, rr, r);
             } else {
                 if (fr && mm == l) x = fv;
             }
@@ -3522,6 +3541,9 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
     b = 0.0;
     if (eq) b = P.r1[i] + (k == 2 ? g0 : 0.0);
     if (tq) b = (sg > 0) ? (-pr.max_torque - bj) : (-pr.max_torque + bj);
+    if constexpr (LM) {  // side 0: tau_min - bbar_j, side 1: bbar_j - tau_max (the line above's bits for -+max_torque)
+        if (tq && lm) b = (sg > 0) ? (lm[WBC_LM_TAU_MIN + k] - bj) : (bj - lm[WBC_LM_TAU_MAX + k]);
+    }
     if (sw) b = sg * (P.rsw[i] + (k == 2 ? g0 : 0.0));
     is_eq = eq;
     // Selection scale and violation tolerance of the reference's own row (the 42-variable row of A
@@ -3547,7 +3569,7 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
         const double dk = P.d[3 * l + k];
         s2 += 2.0 + dl2 - dk * dk;
     }
-    nsel = fr ? 1.0 + pr.friction * pr.friction : s2;
+    nsel = fr ? (LM ? 1.0 + mul * mul : 1.0 + pr.friction * pr.friction) : s2;
     const double bref = (sw && k == 2) ? b - sg * g0 : b;  // the reference row's own bound
     tolv = 1e-10 * fmax(1.0, fabs(bref));
 }
@@ -3740,7 +3762,8 @@ static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing")
 
 // OBJ: as solve16's (the objective from the recovered 42-vector, one entry per lane)
 // DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot)
-template <bool CN = false, bool OBJ = false, bool DU = false>
+// LM: as build_normal's (KernelArgs::lm is null here when the QP's row is not accepted)
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
@@ -3795,7 +3818,9 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
     {
         EST(a, rb, 5);
         double nsel;
-        if constexpr (CN) build_normal<true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN);
+        if constexpr (LM) build_normal<true, true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN,
+                                                   a.lm ? a.lm + (size_t)rb * WBC_LM_LEN : nullptr);
+        else if constexpr (CN) build_normal<true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN);
         else build_normal(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv);
         EST(a, rb, 6);
         double np[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
@@ -4810,7 +4835,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
-template <bool CN = false, bool OBJ = false, bool DU = false>
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -4819,12 +4844,14 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
-constexpr bool fb_writes_dual(int tag) { return tag >= FB_STEP_DU; }  // the duals instances (KernelArgs::dual), contact-normal instances too
+// the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, and lmd0 / lmd1 under a limits table
+constexpr bool fb_writes_dual(int tag) { return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || tag >= FB_STEP_LMD; }
+constexpr bool fb_reads_lm(int tag) { return tag >= FB_STEP_LM; }  // the limits instances (KernelArgs::lm), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
 __device__ __forceinline__ void rp_apply(wbc_params& pv, const wbc_params& base, const double* r, bool bad) {
@@ -4859,7 +4886,16 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
-        solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG), fb_writes_dual(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        if constexpr (fb_reads_lm(TAG)) {
+            // the fallback QP's own limits row: build_normal reads it where it stands; a row the step
+            // does not accept (its robot is flagged) leaves the parameters' friction and max_torque
+            const double* r = ka->lm + (size_t)__builtin_amdgcn_readlane(qp, seg * UPD_SUB) * WBC_LM_LEN;
+            double lv[WBC_LM_LEN];
+#pragma unroll
+            for (int c = 0; c < WBC_LM_LEN; ++c) lv[c] = r[c];
+            f.lm = lm_bad_column(lv) >= 0 ? nullptr : ka->lm;
+        }
+        solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG), fb_writes_dual(TAG), fb_reads_lm(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -4895,11 +4931,21 @@ constexpr bool STEP_DU = true;
 #else
 constexpr bool STEP_DU = false;
 #endif
-template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false>
+// LM (with BB, CN and RP): the limits instances (wbc_kernel_lm0.hip, wbc_kernel_lm1.hip): each
+// lane loads, with its inputs, the bounds of its own two torque rows and its leg's mu from row qp of
+// KernelArgs::lm, indexed as the other rows are; they replace -+max_torque and friction in the lane's
+// rows (solve16's lmv) and in its face.  No face of these instances is read from the workgroup's friction
+// table (CN), so that table is not staged and its 672 B hold the four base-body rows: the LDS is the
+// plain step's.  A fallback callee of their own (FB_STEP_LM).  With WBC_STEP_DUALS (wbc_kernel_lmd0.hip,
+// wbc_kernel_lmd1.hip) they are the duals instances of a wbc_step under a limits table (FB_STEP_LMD): a
+// DU stage behind a run-time test in lm0 / lm1 themselves would raise their fallback callee's frame from
+// bb0's 956 B to du0's 980 B.
+template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
     static_assert(!STEP_DU || (BB && !SONLY), "the duals instances are base-body instances of any mask mix");
+    static_assert(!LM || (BB && !SONLY), "the limits instances are base-body instances of any mask mix");
     __shared__ UpdLds L;
     const int seg = (int)threadIdx.x / UPD_SUB, lane = (int)threadIdx.x % UPD_SUB;
     const int K = a.modes;
@@ -4979,11 +5025,30 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     // the QP's base-body row in the same batch: one entry per lane (lanes past the row reload its last)
     [[maybe_unused]] double bbv = 0.0;
     if constexpr (BB) bbv = a.bb[(size_t)qp * WBC_BB_LEN + (lane < WBC_BB_LEN ? lane : WBC_BB_LEN - 1)];
-    // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy
-    stage_to_lds<LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
+    // the lane's share of the QP's limits row in the same batch (three 8-byte loads): the bound of its
+    // torque rows 16 + lane and 32 + lane (side lane & 1: tau_min or tau_max; the second joint index is
+    // valid in every lane, as solve16's k2) and the mu of its face's leg
+    [[maybe_unused]] double lmv[3];
+    if constexpr (LM) {
+        const double* r = a.lm + (size_t)qp * WBC_LM_LEN;
+        const int side = (lane & 1) ? WBC_LM_TAU_MAX : WBC_LM_TAU_MIN;
+        lmv[0] = r[side + (lane >> 1)];
+        lmv[1] = r[side + 8 + ((lane & 7) >> 1)];
+        lmv[2] = r[WBC_LM_FRICTION + (lane >> 2)];
+    }
+    // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy (the
+    // limits instances: the model alone)
+    static_assert(offsetof(LdsImage, fric) == (LIMG_LEN - FRIC_LEN) * sizeof(double), "the friction table ends the image");
+    stage_to_lds<LM ? LIMG_LEN - FRIC_LEN : LIMG_LEN>(reinterpret_cast<double*>(&L), a.limg, (int)threadIdx.x);
     if (__all(empty)) return;  // the unused tail of a device-built map (uniform)
     [[maybe_unused]] const double* bbr = nullptr;
-    if constexpr (BB) {
+    if constexpr (BB && LM) {
+        // the rows go to LDS before the staging barrier, into the friction table's place (not staged)
+        static_assert(UPD_RPW * WBC_BB_LEN <= FRIC_LEN, "four base-body rows fit the friction table");
+        double* Lbb = &L.fric[seg * WBC_BB_LEN];
+        if (lane < WBC_BB_LEN) Lbb[lane] = bbv;
+        bbr = Lbb;
+    } else if constexpr (BB) {
         // the rows go to LDS before the staging barrier (their loads were issued before the image's, so
         // they are back when it is), 4 x 14 doubles of the workgroup's own beside L
         __shared__ double Lbb[UPD_RPW][WBC_BB_LEN];
@@ -5002,6 +5067,21 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
         const bool bad = rp_bad_column(rpv) >= 0;
         rp_apply(ar.pv, a.pv, rpv, bad);
         if (bad) vin[0] = __builtin_nan("");
+        if constexpr (LM) {
+            // the row's validity (lm_bad_column's two entry rules on what the lanes hold: lanes 2 j and
+            // 2 j + 1 hold tau_min and tau_max of joint j, and of joint 8 + j in the second slot; every mu is
+            // held by four lanes).  A row the step does not accept flags the robot as a bad parameter row
+            // does and leaves the parameters' max_torque and friction in its place
+            const double o0 = seg_shfl(lmv[0], lane ^ 1), o1 = seg_shfl(lmv[1], lane ^ 1);
+            const bool up = (lane & 1) != 0;
+            const bool lbad = seg_any<UPD_SUB>(lm_pair_bad(up ? o0 : lmv[0], up ? lmv[0] : o0) ||
+                                               lm_pair_bad(up ? o1 : lmv[1], up ? lmv[1] : o1) || lm_mu_bad(lmv[2]));
+            if (lbad) {
+                vin[0] = __builtin_nan("");
+                lmv[0] = lmv[1] = up ? ar.pv.max_torque : -ar.pv.max_torque;
+                lmv[2] = ar.pv.friction;
+            }
+        }
         if constexpr (CN) {
             // the lane's face (leg lane >> 2, face lane & 3) from its foot's frame and the robot's mu;
             // a robot with a foot the step does not accept is flagged as one with a bad parameter row
@@ -5012,7 +5092,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
             double fn[3], ft1[3], ft2[3], cnf[3];
             cn_frame(cnm, fn, ft1, ft2);
 #pragma unroll
-            for (int r = 0; r < 3; ++r) cnf[r] = cn_face_elem(fn, ft1, ft2, ar.pv.friction, lane & 3, r);
+            for (int r = 0; r < 3; ++r) cnf[r] = cn_face_elem(fn, ft1, ft2, LM ? lmv[2] : ar.pv.friction, lane & 3, r);
             if constexpr (BB) {
                 // every lane checks its robot's whole row (LDS broadcast reads); a row the step does not
                 // accept flags the robot as above, and the update reads the model's own base meanwhile:
@@ -5026,8 +5106,8 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
                 if (bbad) vin[0] = __builtin_nan("");
                 if (bbad) bbr = &L.model.base_mass;
             }
-            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU>(
-                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr);
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU, LM>(
+                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr, lmv);
         } else
         solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true>(ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg],
                                                                                 nullptr, L.model, &L.fric[0], vin);
@@ -5052,7 +5132,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -5226,7 +5306,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
-template <bool CN, bool OBJ, bool DU>
+template <bool CN, bool OBJ, bool DU, bool LM>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -5253,7 +5333,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
-template <bool CN, bool OBJ, bool DU>
+template <bool CN, bool OBJ, bool DU, bool LM>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -5280,7 +5360,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase<CN, OBJ, DU>(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN, OBJ, DU, LM>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5525,7 +5605,7 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 }  // namespace wbc
 
 #ifdef WBC_STEP_INSTANCE
-// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB]>, in a translation unit
+// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB[, LM]]>, in a translation unit
 // of its own so that its schedule can be chosen apart from the other kernels' (Makefile <UNIT>_KFLAGS):
 // the unit file names the launcher and the template arguments, the engine picks the launcher
 // (wbc_engine.cpp kStepLaunchers, wbc_layout.h step_instance).  The step in one launch: the update

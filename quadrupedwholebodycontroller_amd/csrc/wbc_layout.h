@@ -216,6 +216,14 @@ struct KernelArgs {
     // comment on the declaration's own line: tests/test_modes_objective_cpu.py scans for lines ending in ';'
     // and expects obj to be the last of them)
     double* dual;       // [B][WBC_DUAL_LEN]
+    // Per-robot joint torque bounds and per-foot friction (wbc_set_limits / wbc_bind_device_limits):
+    // [batch][WBC_LM_LEN], row qp for QP qp (tau_min[12], tau_max[12], mu[4]; lm_bad_column below); read
+    // only by the limits instances of the default step (wbc_kernel_lm0.hip, wbc_kernel_lm1.hip), which
+    // are base-body, contact-normal and per-robot-parameter instances too: the engine points bb, cn and
+    // rp at tables of its own where none is in force.  Last, so that no other argument's offset moves.
+    // (Keep the block comment behind the declaration: tests/test_duals_cpu.py cuts lines at the line-comment
+    // mark and expects dual to be the last that then ends in ';'.)
+    const double* lm; /* [B][WBC_LM_LEN] */
 };
 
 // ---------------------------------------------------------------------------------------
@@ -245,16 +253,21 @@ WBC_HD inline int rp_bad_column(const double* r) {
 // 15, in batch order); mode hypotheses or no table for a per-robot-parameter instance; no normals
 // for a contact-normal instance.
 // BB (the base-body instances, a fifth template argument, false for the nine units above): no base-body
-// table.  The second form takes the flags in the template's order (a unit's WBC_STEP_INSTANCE).
-inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false) {
+// table.  LM (the limits instances, a sixth, false for every earlier unit): no limits table.  The other
+// forms take the flags in the template's order (a unit's WBC_STEP_INSTANCE).
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false, bool LM = false) {
     if (a.nwaves <= 0 || (a.stateful != 0) != (STF != 0)) return true;
     if (SONLY && (a.modes || a.qmap)) return true;
     if (RP && (a.modes || !a.rp)) return true;
     if (CN && !a.cn) return true;
-    return BB && !a.bb;
+    if (BB && !a.bb) return true;
+    return LM && !a.lm;
 }
 inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, const KernelArgs& a) {
     return step_args_refused(STF, SONLY, RP, CN, a, BB);
+}
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bool LM, const KernelArgs& a) {
+    return step_args_refused(STF, SONLY, RP, CN, a, BB, LM);
 }
 // The default step's instances, one kernel unit each (wbc_kernel_<unit>.hip): per table in force
 // (none, parameters, parameters + normals; parameters + normals + base bodies in the second list
@@ -282,8 +295,22 @@ enum StepInstanceBB {
 #undef X
     STEP_ALL_INSTANCES
 };
-constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false) {
-    return bb ? (all_stance ? (int)STEP_bbs : stateful ? (int)STEP_bb1 : (int)STEP_bb0)
+// The limits instances (KernelArgs::lm), in a third list for the same reason, whose values
+// go on from STEP_ALL_INSTANCES: the launcher table has STEP_EVERY_INSTANCE entries, built from the three
+// lists in this order.  A limits table comes with the other three (the caller's or the engine's), so lm
+// wins over bb, cn and rp; there is no stance-only unit: an all-stance step runs lm0, whose mask-15
+// waves take the stance form.
+#define WBC_STEP_UNITS_LM(X) X(lm0) X(lm1)
+enum StepInstanceLM {
+    STEP_LM_FIRST_ = STEP_ALL_INSTANCES - 1,
+#define X(unit) STEP_##unit,
+    WBC_STEP_UNITS_LM(X)
+#undef X
+    STEP_EVERY_INSTANCE
+};
+constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false, bool lm = false) {
+    return lm ? (stateful ? (int)STEP_lm1 : (int)STEP_lm0)
+         : bb ? (all_stance ? (int)STEP_bbs : stateful ? (int)STEP_bb1 : (int)STEP_bb0)
          : all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
          : stateful   ? (cn ? STEP_cn1 : rp ? STEP_rp1 : STEP_step1)
                       : (cn ? STEP_cn0 : rp ? STEP_rp0 : STEP_step0);
@@ -388,6 +415,24 @@ WBC_HD inline int bb_bad_entry(const double* r) {
     if (!(a > 0.0)) return WBC_BB_INERTIA;
     if (!(a * d - b * b > 0.0)) return WBC_BB_INERTIA + 4;
     if (!(a * (d * f - e * e) - b * (b * f - e * c) + c * (b * e - d * c) > 0.0)) return WBC_BB_INERTIA + 8;
+    return -1;
+}
+// A limits row (wbc.h WBC_LM_*: tau_min[12], tau_max[12], mu[4]) the step accepts: -1, or the first
+// column that fails: a non-finite entry at its own column, tau_min[j] > tau_max[j] at tau_max's
+// (equal bounds are a dead or locked-torque actuator and valid), mu[l] < 0 at mu's.  One definition for
+// the host's validation (wbc_set_limits) and the kernels' (a device-bound row): the kernels hold a row
+// spread over a segment's lanes and apply the two entry rules, lm_pair_bad and lm_mu_bad, to what each
+// lane holds.
+WBC_HD inline bool lm_pair_bad(double lo, double hi) {
+    return !__builtin_isfinite(lo) || !__builtin_isfinite(hi) || !(lo <= hi);
+}
+WBC_HD inline bool lm_mu_bad(double mu) { return !__builtin_isfinite(mu) || mu < 0.0; }
+WBC_HD inline int lm_bad_column(const double* r) {
+    for (int c = 0; c < WBC_LM_LEN; ++c) {
+        if (!__builtin_isfinite(r[c])) return c;
+        if (c >= WBC_LM_TAU_MAX && c < WBC_LM_FRICTION && lm_pair_bad(r[c - WBC_LM_TAU_MAX + WBC_LM_TAU_MIN], r[c])) return c;
+        if (c >= WBC_LM_FRICTION && lm_mu_bad(r[c])) return c;
+    }
     return -1;
 }
 WBC_HD inline int32_t qmap_entry(int qp, int mask) { return (int32_t)((qp << 4) | (mask & 15)); }
