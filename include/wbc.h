@@ -476,6 +476,39 @@ int32_t wbc_bind_device_limits(wbc_engine* h, const double* d_table);
  * in force, else from wbc_params. */
 int32_t wbc_get_limits(wbc_engine* h, double* table);
 
+/* Per-foot bounds on the normal contact force (contact load ramps: a gait scheduler unloads a foot
+ * before lift-off by lowering fn_max to 0 over the last cycles of stance and raises it again after
+ * touchdown; fn_min keeps a minimum load on a foot that must not slip): a table of doubles, row-major
+ * [B][WBC_FN_LEN], row b for robot b, in newtons.  Rows are 64 bytes.  While a force-bound table is in
+ * force the QP of robot b gains, per stance foot l,
+ *     fn_min[l] <= n_l . f_l <= fn_max[l],
+ * n_l the unit contact normal of foot l (m_l / |m_l| under contact normals, else e_z).  fn_min = -inf
+ * and fn_max = +inf mean "no row": the row (-inf x 4, +inf x 4), which wbc_get_force_bounds returns
+ * without a table, gives the step without the table bit for bit.  A row is invalid when an entry is
+ * NaN, fn_min[l] = +inf, fn_max[l] = -inf or fn_min[l] > fn_max[l] (equal bounds are valid).  A valid
+ * row without a feasible point (fn_max < 0, say) is the solver's business: WBC_QP_INFEASIBLE.  In the
+ * hotstart's row numbering the rows are 40 + 2 l (n.f >= fn_min) and 41 + 2 l (n.f <= fn_max). */
+enum {
+    WBC_FN_MIN = 0, /* [4] lower bound of n_l . f_l per foot (LH, LF, RF, RH), N; -inf: none */
+    WBC_FN_MAX = 4, /* [4] upper bound; +inf: none */
+    WBC_FN_LEN = 8
+};
+/* Host table, validated and then copied on the engine stream (the call synchronizes it).  An invalid
+ * row returns WBC_ERR_ARG, wbc_last_error names the row and the column, and the previous table stays
+ * in force.  NULL: back to no table of the engine's own (a bound device table stays in force).
+ * Supported under the table: the default wbc_step (stateless, stateful, WBC_COLD, WBC_NO_X, WBC_GROUP)
+ * and the plain wbc_cycle, with any of the other per-robot tables in force.  Refused with
+ * WBC_ERR_STATE: wbc_update, wbc_solve, wbc_step_modes, wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED
+ * or WBC_RESIDENT, and wbc_step with WBC_DUALS (a binding force row has no entry among the 40
+ * multipliers). */
+int32_t wbc_set_force_bounds(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_FN_LEN] (no copy, no host validation; 16-byte aligned; a caller may
+ * rewrite it on the engine's stream every cycle).  NULL restores the engine-owned table, or none.  On
+ * the device an invalid row gives that robot WBC_QP_NUMERIC and zero outputs; no other robot is touched. */
+int32_t wbc_bind_device_force_bounds(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_FN_LEN] to the host (synchronous); without one (-inf x 4, +inf x 4). */
+int32_t wbc_get_force_bounds(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

@@ -39,10 +39,15 @@ BB_COLUMN_NAMES = ("mass", "com_x", "com_y", "com_z", "I_xx", "I_xy", "I_xz", "I
 LM_LEN = 28
 LM_TAU_MIN, LM_TAU_MAX, LM_FRICTION = 0, 12, 24
 LIMIT_NAMES = ("tau_min", "tau_max", "friction")
+# the per-foot normal-force bound table (WBC_FN_* in include/wbc.h): fn_min[4], fn_max[4] (LH, LF, RF, RH), N;
+# -inf / +inf: no bound
+FN_LEN = 8
+FN_MIN, FN_MAX = 0, 4
+FORCE_BOUND_NAMES = ("fn_min", "fn_max")
 
 # the per-robot tables of the default step: name -> row length; the C entry points of table <name> are
 # wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
-TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN, "limits": LM_LEN}
+TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN, "limits": LM_LEN, "force_bounds": FN_LEN}
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
 # the objective and best-mode outputs of wbc_step_modes (WBC_OBJECTIVE / WBC_BEST)
 MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
@@ -397,6 +402,57 @@ def limits_table(batch: int, defaults, table) -> np.ndarray:
     return np.ascontiguousarray(out)
 
 
+def force_bounds_row(fn_min=-np.inf, fn_max=np.inf) -> np.ndarray:
+    """One (FN_LEN,) row of the force-bound table: fn_min and fn_max a scalar or (4,) (feet LH, LF, RF, RH), in
+    newtons along each foot's contact normal; -inf / +inf (the defaults) mean no bound."""
+    row = np.empty(FN_LEN)
+    for name, v, at in (("fn_min", fn_min, FN_MIN), ("fn_max", fn_max, FN_MAX)):
+        v = np.asarray(v, np.float64)
+        if v.shape not in ((), (4,)):
+            raise ValueError(f"force bounds {name}: need a scalar or shape (4,), got {v.shape}")
+        row[at:at + 4] = v
+    return row
+
+
+def force_bounds_bad_column(row) -> int:
+    """The validity rule of one force-bound row (wbc_layout.h fn_bad_column): -1, or the first failing column:
+    NaN or +inf in fn_min, NaN or -inf in fn_max, fn_min > fn_max (at fn_max's column)."""
+    r = np.asarray(row, np.float64)
+    for c in range(FN_LEN):
+        if c < FN_MAX and not r[c] < np.inf:
+            return c
+        if c >= FN_MAX and (not r[c] > -np.inf or not r[c - FN_MAX + FN_MIN] <= r[c]):
+            return c
+    return -1
+
+
+def force_bounds_table(batch: int, defaults, table) -> np.ndarray:
+    """The [B, FN_LEN] table of wbc_set_force_bounds from a (B, 8) array, one (8,) row broadcast to all robots,
+    or a dict of FORCE_BOUND_NAMES -> a scalar, one (4,) vector, a (B,) value per robot or a (B, 4) array, whose
+    missing entries take the rows of `defaults` ((B, 8): Engine.force_bounds()).  The engine validates it."""
+    B = int(batch)
+    out = np.array(np.broadcast_to(np.asarray(defaults, np.float64), (B, FN_LEN)))
+    if isinstance(table, dict):
+        unknown = sorted(set(table) - set(FORCE_BOUND_NAMES))
+        if unknown:
+            raise ValueError(f"unknown force bound entries {unknown}; entries are {FORCE_BOUND_NAMES}")
+        for name, at in (("fn_min", FN_MIN), ("fn_max", FN_MAX)):
+            if name not in table:
+                continue
+            v = np.asarray(table[name], np.float64)
+            if v.shape == (B,) and B != 4:
+                v = v[:, None]
+            elif v.shape not in ((), (4,), (B, 4)):
+                raise ValueError(f"force bounds {name}: need a scalar, shape (4,), ({B},) or ({B}, 4), got {v.shape}")
+            out[:, at:at + 4] = v
+    else:
+        t = np.asarray(table, np.float64)
+        if t.shape not in ((FN_LEN,), (B, FN_LEN)):
+            raise ValueError(f"force bounds table: need shape ({B}, {FN_LEN}) or ({FN_LEN},), got {t.shape}")
+        out[:, :] = t
+    return np.ascontiguousarray(out)
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -543,6 +599,26 @@ class Engine:
         """wbc_get_limits: the [B, 28] table in force (without one: -max_torque x 12, +max_torque x 12 and
         friction x 4 per robot, from its parameter row or the engine-wide params)."""
         return self._get_table("limits")
+
+    def set_force_bounds(self, table):
+        """wbc_set_force_bounds: per-foot bounds fn_min <= n . f <= fn_max on the normal contact force of
+        every stance foot, for the default step (contact load ramps).  `table`: a (B, 8) array, one (8,) row
+        (force_bounds_row), or a dict {fn_min, fn_max} of scalars, (4,) vectors or per-robot arrays
+        (force_bounds_table), whose missing entries keep what force_bounds() returns now; -inf / +inf mean
+        no bound.  Validation is the engine's (WbcError names the row and column).  None clears the table."""
+        self._set_table("force_bounds", None if table is None else
+                        force_bounds_table(self.batch, self.force_bounds() if isinstance(table, dict) else 0.0, table))
+
+    def bind_device_force_bounds(self, table=0):
+        """wbc_bind_device_force_bounds: a caller-owned device table [B, 8] of doubles (no copy, no host
+        validation; it may be rewritten on the engine's stream every cycle, as a load ramp is): an integer
+        device pointer, or an object with data_ptr() (a torch tensor), which the engine keeps referenced while
+        it is bound.  0 / None: the engine-owned table, or none."""
+        self._bind_table("force_bounds", table)
+
+    def force_bounds(self) -> np.ndarray:
+        """wbc_get_force_bounds: the [B, 8] table in force (without one: -inf x 4, +inf x 4 per robot)."""
+        return self._get_table("force_bounds")
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <new>
 #include <string>
@@ -25,16 +26,19 @@ extern "C" hipError_t wbc_launch_solve_general(const wbc::KernelArgs* a, hipStre
 extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStream_t st);
 // The default step's launchers (wbc_launch_update_solve_<unit> of wbc_kernel_<unit>.hip), indexed by
 // wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's; the base-body units'
-// (WBC_STEP_UNITS_BB) follow the nine, the limits units' (WBC_STEP_UNITS_LM) those
+// (WBC_STEP_UNITS_BB) follow the nine, the limits units' (WBC_STEP_UNITS_LM) those, the force-bound units'
+// (WBC_STEP_UNITS_FN) the limits units'
 #define X(unit) extern "C" hipError_t wbc_launch_update_solve_##unit(const wbc::KernelArgs* a, hipStream_t st);
 WBC_STEP_UNITS(X)
 WBC_STEP_UNITS_BB(X)
 WBC_STEP_UNITS_LM(X)
+WBC_STEP_UNITS_FN(X)
 #undef X
 #define X(unit) wbc_launch_update_solve_##unit,
-static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X) WBC_STEP_UNITS_LM(X)};
+static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X) WBC_STEP_UNITS_LM(X)
+                                                                                       WBC_STEP_UNITS_FN(X)};
 #undef X
-static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_EVERY_INSTANCE, "one launcher per instance");
+static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_LAUNCHER_COUNT, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 // the mode loop's objective instance (wbc_kernel_modes_obj.hip) and the selection after it (WBC_BEST)
 extern "C" hipError_t wbc_launch_modes_obj(const wbc::KernelArgs* a, hipStream_t st);
@@ -150,6 +154,10 @@ struct wbc_engine {
     // and friction).  The kernels that read them are base-body instances, so without a base-body table in
     // force their step reads d_bb_def, and d_cn_flat / d_rp_uni as the base-body kernels do
     RobotTable lm{WBC_LM_LEN};
+    // per-foot normal-force bounds (KernelArgs::fn, [B][WBC_FN_LEN]; without: no such rows).  The kernels that
+    // read them are limits and base-body instances; without a limits table in force they take each robot's
+    // own -+max_torque and friction (a null KernelArgs::lm), the other tables as the limits kernels do
+    RobotTable fn{WBC_FN_LEN};
     // bound (possibly external) inputs
     wbc::ConstInputView in{};
     // state / outputs
@@ -218,10 +226,12 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force || h->lm.in_force) ? h->d_rp_uni : nullptr);
-    a.cn = h->cn.in_force ? h->cn.in_force : ((h->bb.in_force || h->lm.in_force) ? h->d_cn_flat : nullptr);
-    a.bb = h->bb.in_force ? h->bb.in_force : (h->lm.in_force ? h->d_bb_def : nullptr);
+    const bool lf = h->lm.in_force || h->fn.in_force;  // limits or force bounds: their kernels read rp, cn and bb
+    a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force || lf) ? h->d_rp_uni : nullptr);
+    a.cn = h->cn.in_force ? h->cn.in_force : ((h->bb.in_force || lf) ? h->d_cn_flat : nullptr);
+    a.bb = h->bb.in_force ? h->bb.in_force : (lf ? h->d_bb_def : nullptr);
     a.lm = h->lm.in_force;
+    a.fn = h->fn.in_force;
     a.base_pose = in.pose;
     a.nu = in.nu;
     a.qj = in.qj;
@@ -437,7 +447,7 @@ hipError_t launch_solves(wbc_engine* h, wbc::KernelArgs& a) {
 
 // The per-robot tables are read by the default wbc_step (and the plain wbc_cycle) only: with one in
 // force `call` is refused, outright (forms = 0) or when `flags` ask for one of `forms`.  The
-// parameter table is named before the normals, then the base bodies, the limits last; `allowed` says
+// parameter table is named before the normals, then the base bodies, the limits, the force bounds last; `allowed` says
 // what the call may still do.
 int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uint32_t forms, const char* allowed) {
     if (forms && !(flags & forms)) return WBC_OK;
@@ -447,6 +457,7 @@ int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uin
         {&wbc_engine::cn, "contact normals", " are in force", "them with wbc_set_contact_normals"},
         {&wbc_engine::bb, "a per-robot base body table", " is in force", "it with wbc_set_base_body"},
         {&wbc_engine::lm, "per-robot limits", " are in force", "them with wbc_set_limits"},
+        {&wbc_engine::fn, "per-foot force bounds", " are in force", "them with wbc_set_force_bounds"},
     };
     for (const auto& t : kTables) {
         if (!(h->*t.table).in_force) continue;
@@ -609,7 +620,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
-                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own};
+                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own, h->fn.own};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -899,6 +910,29 @@ int32_t wbc_get_limits(wbc_engine* h, double* table) {
     return WBC_OK;
 }
 
+static std::string fn_row_error(const double* row) {
+    const int c = wbc::fn_bad_column(row);
+    if (c < 0) return "";
+    const char* group = c < WBC_FN_MAX ? "fn_min" : "fn_max";
+    char val[32];
+    std::snprintf(val, sizeof(val), "%g", row[c]);
+    return "column " + std::to_string(c) + " (" + group + "[" + std::to_string(c % WBC_NUM_LEGS) + "]) = " + val +
+           ": need no NaN, fn_min < +inf, fn_max > -inf and fn_min <= fn_max per foot";
+}
+// The force-bound kernels read the parameter, normal and base-body tables too (the engine's own where none
+// is in force) and take a null limits table (each robot's own -+max_torque and friction)
+int32_t wbc_set_force_bounds(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::fn, table, "wbc_set_force_bounds", "d_fn", fn_row_error, ensure_rp_cn_bb_uniform);
+}
+int32_t wbc_bind_device_force_bounds(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::fn, d_table, "wbc_bind_device_force_bounds", ensure_rp_cn_bb_uniform);
+}
+int32_t wbc_get_force_bounds(wbc_engine* h, double* table) {
+    const double inf = std::numeric_limits<double>::infinity();
+    const double none[WBC_FN_LEN] = {-inf, -inf, -inf, -inf, inf, inf, inf, inf};
+    return table_get(h, &wbc_engine::fn, table, none);
+}
+
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
@@ -953,6 +987,9 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     const bool duals = (flags & WBC_DUALS) != 0;
     if (duals && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
+    if (duals && h->fn.in_force)
+        return fail(WBC_ERR_STATE, "wbc_step: WBC_DUALS with per-foot force bounds in force (the 40 multipliers have no entry "
+                                   "for a force row; clear them with wbc_set_force_bounds(h, NULL))");
     h->step_duals = false;
     if (duals) {  // the engine's own tables for the ones the caller has not set, and the buffer
         if (const int32_t rc = ensure_rp_cn_bb_uniform(h)) return rc;
@@ -993,7 +1030,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_du1 : wbc_launch_update_solve_du0)(&a, h->stream));
         } else {
             WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr,
-                                                      a.lm != nullptr)](&a, h->stream));
+                                                      a.lm != nullptr, a.fn != nullptr)](&a, h->stream));
         }
     }
     if (timed) {

@@ -9,6 +9,7 @@
 // (WBC_STEP_DUALS), whose solves also write the QP multipliers of the friction and torque rows (20).
 // Four more hold the instances under per-robot torque bounds and per-foot friction, a sixth template
 // argument LM (21): lm0 and lm1, and lmd0 and lmd1, the same with WBC_STEP_DUALS.
+// Two more hold the instances under per-foot normal-force bounds, a seventh template argument FN (22): fn0 and fn1.
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -53,6 +54,7 @@ namespace wbc {
 
 constexpr int NQ = 24;                  // reduced QP variables
 constexpr int C0_LANES = 52;            // max constraints: 7 ns + 24 + 6 (4 - ns) <= 52
+constexpr int C0X_LANES = 8;            // and under force bounds 2 ns more (SolveLdsFn): <= 60 of the wave's 64 lanes
 
 // Frames and bodies are read one per lane (lane = body): 25 doubles (50 dwords) apart puts 13
 // consecutive lanes in distinct LDS banks, where 24 doubles (48 dwords) put every 4th lane in the
@@ -1779,12 +1781,28 @@ __device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]
 // (joint l >> 1: tau_min on side 0, tau_max on side 1), of row 32 + l (joint 8 + (l & 7 >> 1)) and the mu
 // of its face's leg; they stand in for -+max_torque and friction.  Another lane's row is never rebuilt
 // from its bound: its slack comes from the owner lane and, under CN, so does its face.
-template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
+// FN (with LM; the force-bound instances, wbc_kernel_fn0.hip / wbc_kernel_fn1.hip, KernelArgs::fn):
+// the third slot of lanes 8..15, empty otherwise, holds the two-sided bound on a stance foot's normal force:
+// lane l = 8 + 2 leg + side holds row 32 + l = 40 + 2 leg + side, side 0 n . f >= fn_min, side 1
+// -n . f >= -fn_max.  fnv[0] is the lane's bound (infinite: no row; lanes < 8 hold an infinite one), fnv[1..3]
+// the unit contact normal of the row's leg (l - 8) >> 1, which is not the leg of the lane's face.  Another
+// lane's row comes from its owner lane's registers as a face does under CN (fn_row), and its dot with a
+// column of J reads the column's three entries at the row's leg.
+template <bool FN>
+__device__ __forceinline__ void fn_row(const double* cnf, const double* fne, int p, double (&e)[3]) {
+    // the three entries of row p from lane p & 15: its face (p < 16) or its signed normal (p >= 40); one
+    // shuffle per entry either way, the source selected in the owner lane
+#pragma unroll
+    for (int r = 0; r < 3; ++r) e[r] = seg_shfl((FN && p >= 40) ? fne[r] : cnf[r], p & 15);
+}
+template <bool ROWS, bool GEN, int STF = -1, bool RP = false, bool CN = false, bool OBJ = false, bool DU = false, bool LM = false,
+          bool FN = false>
 __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, const Prob& P, UpdScratch& s,
                         const St16& V, int kap, int status0, double hws_lo = 0.0, double hws_hi = 0.0,
                         double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr,
-                        [[maybe_unused]] const double* lmv = nullptr) {
+                        [[maybe_unused]] const double* lmv = nullptr, [[maybe_unused]] const double* fnv = nullptr) {
     static_assert(!LM || CN, "the limits instances are contact-normal instances");
+    static_assert(!FN || (LM && !DU && !OBJ), "the force-bound instances are limits instances without duals");
     constexpr int N = 12;
     constexpr int NTS = GEN ? 12 : NTS_ST;  // Nt row stride
     const wbc_params& pr = a.pv;
@@ -1796,7 +1814,17 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
 
     // normals (force space) of the three slots, as solve_stance / build_normal
     const int fl = l >> 2, rr = l & 3, k1 = l >> 1, k2 = 8 + ((l & 7) >> 1);
-    const bool v2 = l < 8;
+    // FN: the lane's force row exists iff its bound is finite and its leg (l - 8) >> 1 is in stance; fne is
+    // its normal in the >=-form (+n on side 0, -n on side 1), zero where there is no row
+    [[maybe_unused]] const int fl2 = ((l - 8) >> 1) & 3;
+    [[maybe_unused]] bool fex = false;
+    [[maybe_unused]] double fne[3] = {0.0, 0.0, 0.0};
+    if constexpr (FN) {
+        fex = l >= 8 && fabs(fnv[0]) < __builtin_inf() && ((kap >> fl2) & 1) != 0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) fne[r] = fex ? ((l & 1) ? -fnv[1 + r] : fnv[1 + r]) : 0.0;
+    }
+    const bool v2 = FN ? (l < 8 || fex) : l < 8;
     const bool fon = GEN ? (((kap >> fl) & 1) != 0) : true;  // friction faces exist for stance legs only
     const double sg = (l & 1) ? -1.0 : 1.0;
     double n0[N], n1[N], n2[N];
@@ -1809,17 +1837,23 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
         else n0[m] = (m / 3 == fl) ? fv : 0.0;
         n1[m] = -sg * V.Nt[k1 * NTS + m];
         const double nt2 = V.Nt[k2 * NTS + m];  // (k2 is a valid row in every lane: loaded, then masked)
-        n2[m] = v2 ? -sg * nt2 : 0.0;
+        if constexpr (FN) n2[m] = (l < 8) ? -sg * nt2 : ((m / 3 == fl2) ? fne[r] : 0.0);
+        else n2[m] = v2 ? -sg * nt2 : 0.0;
     }
     // (LM: side 0 is tau_min - t0, side 1 t0 - tau_max; with -+max_torque the bits of the line below)
     const double bp1 = LM ? sg * (lmv[0] - V.t0[k1]) : -pr.max_torque - sg * V.t0[k1];
-    const double bp2 = LM ? sg * (lmv[1] - V.t0[k2]) : -pr.max_torque - sg * V.t0[k2];
+    // (FN: side 0 is fn_min, side 1 -fn_max; the row's own tolerance and a selection norm of 1, the unit
+    // normal's in the reference's 42-variable space)
+    const double bp2t = LM ? sg * (lmv[1] - V.t0[k2]) : -pr.max_torque - sg * V.t0[k2];
+    const double bp2 = (FN && l >= 8) ? (fex ? sg * fnv[0] : 0.0) : bp2t;
     const double tol0 = 1e-10;
     const double tol1 = 1e-10 * fmax(1.0, fabs(LM ? lmv[0] - P.bbj[k1] : -pr.max_torque - sg * P.bbj[k1]));
-    const double tol2 = 1e-10 * fmax(1.0, fabs(LM ? lmv[1] - P.bbj[k2] : -pr.max_torque - sg * P.bbj[k2]));
+    const double tol2t = 1e-10 * fmax(1.0, fabs(LM ? lmv[1] - P.bbj[k2] : -pr.max_torque - sg * P.bbj[k2]));
+    const double tol2 = (FN && l >= 8) ? 1e-10 * fmax(1.0, fex ? fabs(fnv[0]) : 1.0) : tol2t;
     const double mu0 = LM ? lmv[2] : pr.friction;
     const double in0 = fast_rsq(fmax(1.0 + mu0 * mu0, 1e-300));
-    const double in1 = fast_rsq(fmax(V.nsel[k1], 1e-300)), in2 = fast_rsq(fmax(V.nsel[k2], 1e-300));
+    const double in1 = fast_rsq(fmax(V.nsel[k1], 1e-300)), in2t = fast_rsq(fmax(V.nsel[k2], 1e-300));
+    const double in2 = (FN && l >= 8) ? 1.0 : in2t;
     double sp0, sp1, sp2;
     auto slacks = [&](const double* xv) {
         double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0}, q2[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1951,6 +1985,12 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
 #pragma unroll
             for (int lg = 0; lg < 4; ++lg)
                 if ((kap >> lg) & 1) keep |= 0xFull << (4 * lg);
+            if constexpr (FN) {
+                // the force rows that still exist (a finite bound, the leg in contact): lanes 8..15 of the
+                // segment are bits 40..47
+                const unsigned fb = (unsigned)(__ballot(fex) >> ((int)threadIdx.x & 48)) & 0xFF00u;
+                keep |= (unsigned long long)fb << 32;
+            }
             ws &= keep;
             const int nw = __popcll(ws);
             // Direct check for a warm set of one or two rows (the trot's: 88 % of its QPs carry no
@@ -1977,6 +2017,20 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double* nrow = V.Nt + (frc ? fo : to);
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     nn = 0.0;
+                    if constexpr (FN) {
+                        // a third kind, p >= 40: the signed unit normal at the row's leg, from its owner lane
+                        const bool frn = p >= 40;
+                        const int lg = frn ? ((p - 40) >> 1) & 3 : (p & 15) >> 2;
+                        const int tf = frn ? 0 : to;
+                        double e[3];
+                        fn_row<FN>(cnf, fne, p, e);
+#pragma unroll
+                        for (int k = 0; k < N; ++k) {
+                            np[k] = (frc || frn) ? ((k / 3 == lg) ? e[k % 3] : 0.0) : sgn * V.Nt[tf + k];
+                            nn = fma(np[k], np[k], nn);
+                        }
+                        return;
+                    }
                     if constexpr (CN) {
                         double e[3];
                         cn_face<CN>(cnf, p, e);
@@ -2082,7 +2136,18 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                     const double* nrow = frc ? &V.fric[FRIC_ROW(p)] : &V.Nt[(tq >> 1) * NTS];
                     const double sgn = (frc || (tq & 1)) ? 1.0 : -1.0;
                     double np[N], nn = 0.0;
-                    if constexpr (CN) {
+                    if constexpr (FN) {
+                        const bool frn = p >= 40;
+                        const int lg = frn ? ((p - 40) >> 1) & 3 : (p & 15) >> 2;
+                        double e[3];
+                        fn_row<FN>(cnf, fne, p, e);
+                        const double* trow = &V.Nt[(frn ? 0 : (tq >> 1)) * NTS];
+#pragma unroll
+                        for (int k = 0; k < N; ++k) {
+                            np[k] = (frc || frn) ? ((k / 3 == lg) ? e[k % 3] : 0.0) : sgn * trow[k];
+                            nn = fma(np[k], np[k], nn);
+                        }
+                    } else if constexpr (CN) {
                         double e[3];
                         cn_face<CN>(cnf, p, e);
                         const double* trow = &V.Nt[(tq >> 1) * NTS];
@@ -2209,7 +2274,22 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                 // dot then ends in one add instead of three)
                 double a2[2] = {0.0, 0.0};
                 double dn;
-                if constexpr (CN) {
+                [[maybe_unused]] bool frn = false;  // FN: a force row (p >= 40), its sign in its entries
+                if constexpr (FN) {
+                    // as the CN branch below, with the third kind: three entries from the owner lane (its
+                    // face or its signed normal) against the column's three at the row's leg
+                    frn = pstar >= 40;
+                    double e[3];
+                    fn_row<FN>(cnf, fne, pstar, e);
+                    const int lg = frn ? ((pstar - 40) >> 1) & 3 : (pstar & 15) >> 2;
+                    const double* jf = &Jl[3 * lg * JMS + i];
+                    const double j0 = jf[0], j1 = jf[JMS], j2 = jf[2 * JMS];
+                    const double* trow = V.Nt + ((frc || frn) ? 0 : to);
+#pragma unroll
+                    for (int k = 0; k < N; ++k) a2[k & 1] = fma(jc[k], trow[k], a2[k & 1]);
+                    const double df = fma(j2, e[2], fma(j0, e[0], 0.0)) + fma(j1, e[1], 0.0);
+                    dn = (frc || frn) ? df : a2[0] + a2[1];
+                } else if constexpr (CN) {
                     // a friction face: its three entries from the owner lane, against the column's
                     // three entries at the face's leg (a 12-long dot with nine zeros, term for term);
                     // a torque row: the row of Nt as before
@@ -2228,7 +2308,8 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                         a2[k & 1] = fma(jc[k], fric_elem<RP>(nrow[k], frc, (pstar & 15) >> 2, k, pr.friction), a2[k & 1]);
                     dn = a2[0] + a2[1];
                 }
-                dj = ((l < N) ? ((frc || (tq & 1)) ? 1.0 : -1.0) : 0.0) * dn;
+                if constexpr (FN) dj = ((l < N) ? ((frc || frn || (tq & 1)) ? 1.0 : -1.0) : 0.0) * dn;
+                else dj = ((l < N) ? ((frc || (tq & 1)) ? 1.0 : -1.0) : 0.0) * dn;
             }
             const double sps = seg_shfl(sel3d(js, sp0, sp1, sp2), ol);
             IST(0);  // the chosen row's normal
@@ -2296,7 +2377,16 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                         if (k >= l1 && k < q) {
                             const int pl = seg_shfl_i(act, k);
                             double nl;  // component i of row pl's normal
-                            if constexpr (CN) {
+                            if constexpr (FN) {
+                                const int pc = pl < 0 ? 0 : pl;
+                                const bool frn = pc >= 40;
+                                double e[3];
+                                fn_row<FN>(cnf, fne, pc, e);
+                                const int qt = (pc < 16 || frn) ? 0 : pc - 16;
+                                const double tn = ((qt & 1) ? 1.0 : -1.0) * V.Nt[(qt >> 1) * NTS + i];
+                                const int lg = frn ? ((pc - 40) >> 1) & 3 : pc >> 2;
+                                nl = (pc < 16 || frn) ? ((i / 3 == lg) ? sel3(e, i % 3) : 0.0) : tn;
+                            } else if constexpr (CN) {
                                 double e[3];
                                 cn_face<CN>(cnf, pl < 0 ? 0 : pl, e);
                                 const int qt = pl < 16 ? 0 : pl - 16;
@@ -2476,7 +2566,7 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
         const unsigned long long b0 = __ballot((ab & 1) != 0), b1 = __ballot((ab & 2) != 0), b2 = __ballot((ab & 4) != 0);
         const int sh = (int)threadIdx.x & 48;
         const unsigned long long ws = ((b0 >> sh) & 0xFFFFull) | (((b1 >> sh) & 0xFFFFull) << 16) |
-                                      (((b2 >> sh) & 0xFFull) << 32);
+                                      (((b2 >> sh) & (FN ? 0xFFFFull : 0xFFull)) << 32);  // (FN: rows 40..47 too)
         if (l == 0) {
             double* H = a.hist + (size_t)rb * HIST_LEN;
             H[H_WSLO] = ok ? (double)(unsigned)(ws & 0xffffffffull) : 0.0;
@@ -2530,13 +2620,15 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false, bool LM = false>
+          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
                              [[maybe_unused]] const double* cnf = nullptr, [[maybe_unused]] const double* bbr = nullptr,
-                             [[maybe_unused]] const double* lmv = nullptr) {
+                             [[maybe_unused]] const double* lmv = nullptr, [[maybe_unused]] const double* fnv = nullptr) {
     const wbc_params& pr = a.pv;
+    // FN (the force-bound instances, KernelArgs::fn): fnv is the lane's bound and its row's unit normal, handed
+    // on to solve16 as lmv is
     // LM (the limits instances, KernelArgs::lm): lmv is the lane's share of its robot's limits row, handed
     // on to solve16; the update itself reads neither bound nor mu
     // BB (the base-body instances, KernelArgs::bb): bbr is the robot's base body, 13 doubles laid out as
@@ -3387,6 +3479,8 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
             double hrow[12], gsv = 0.0;
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
+                if constexpr (FN) solve16<true, false, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf, lmv, fnv);
+                else
                 solve16<true, false, STF, RP, CN, false, DU, LM>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf, lmv);
                 return true;
             }
@@ -3397,6 +3491,9 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         bool vac = false;
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
+            if constexpr (FN) solve16<true, true, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
+                                                                                    hWlo, hWhi, hWtag, cnf, lmv, fnv);
+            else
             solve16<true, true, STF, RP, CN, false, DU, LM>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
                                                             hWlo, hWhi, hWtag, cnf, lmv);
             return true;
@@ -3481,17 +3578,25 @@ __device__ __forceinline__ int nth_leg(int kap, int idx, int want) {
 // (cn_frame; a foot the step does not accept stands on flat ground: its robot is flagged)
 // LM: lm is the QP's row of KernelArgs::lm (null for a row the step does not accept: its robot is flagged
 // and pr's values stand): torque row (j, side) takes tau_min[j] / tau_max[j], a face of leg l mu[l]
-template <bool CN = false, bool LM = false>
+// FN: fnb is the QP's row of KernelArgs::fn (null for a row the step does not accept); mp.m counts, after the
+// swing rows (the oracle appends them to the reference's rows), two rows per stance leg: side 0
+// n_l . f_l >= fn_min[l], side 1 -n_l . f_l >= -fn_max[l], n_l the foot's unit normal (cn_frame).  A row
+// whose bound is infinite (or whose table row is not accepted) is no constraint: tolv = -1 says so
+template <bool CN = false, bool LM = false, bool FN = false>
 __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& mp, const wbc_params& pr, int p,
                              double* n, double& b, bool& is_eq, double& nsel, double& tolv,
-                             [[maybe_unused]] const double* cn = nullptr, [[maybe_unused]] const double* lm = nullptr) {
+                             [[maybe_unused]] const double* cn = nullptr, [[maybe_unused]] const double* lm = nullptr,
+                             [[maybe_unused]] const double* fnb = nullptr) {
+    static_assert(!FN || (CN && LM), "the force-bound instances are limits and contact-normal instances");
     const int kap = mp.kap;
     const int t_fr = mp.neq, t_tq = mp.neq + mp.nfr, t_sw = t_tq + mp.ntq;
+    [[maybe_unused]] const int t_fn = t_sw + 6 * mp.nsw;
     const bool in = p < mp.m;
     const bool eq = in && p < t_fr;
     const bool fr = in && p >= t_fr && p < t_tq;
     const bool tq = in && p >= t_tq && p < t_sw;
-    const bool sw = in && p >= t_sw;
+    const bool sw = FN ? (in && p >= t_sw && p < t_fn) : (in && p >= t_sw);
+    [[maybe_unused]] const bool fnr = FN && in && p >= t_fn;
     // per type: leg l, component k / friction face rr, row i, sign
     int l = 0, k = 0, rr = 0;
     double sg = 1.0;
@@ -3499,6 +3604,9 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
     if (fr) { const int q = p - t_fr; l = nth_leg(kap, q / 4, 1); rr = q % 4; }
     if (tq) { const int q = p - t_tq; k = q / 2; sg = (q & 1) ? -1.0 : 1.0; }
     if (sw) { const int q = p - t_sw; l = nth_leg(kap, q / 6, 0); k = (q % 6) / 2; sg = (q & 1) ? -1.0 : 1.0; }
+    if constexpr (FN) {
+        if (fnr) { const int q = p - t_fn; l = nth_leg(kap, q / 2, 1); sg = (q & 1) ? -1.0 : 1.0; }
+    }
     const int i = tq ? k : 3 * l + k;  // Jbj / Mbj row (torque: joint index)
     // qdd part: +-Jbj row i (R1, R4/R5) or +-Mbj row i (R3)
     const double* row = (tq ? P.Mbj : P.Jbj) + i * 12;
@@ -3533,6 +3641,9 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
                 if (fr && mm == l) x = fv;
             }
             if (sw && mm == l && r == k) x = 1.0;  // the slack of swing leg l
+            if constexpr (FN) {
+                if (fnr && mm == l) x = sg * cnn[r];  // +-the foot's unit normal
+            }
             n[12 + 3 * mm + r] = x;
         }
     }
@@ -3572,6 +3683,19 @@ __device__ void build_normal(const Prob& P, const double (*G)[12], const QpMap& 
     nsel = fr ? (LM ? 1.0 + mul * mul : 1.0 + pr.friction * pr.friction) : s2;
     const double bref = (sw && k == 2) ? b - sg * g0 : b;  // the reference row's own bound
     tolv = 1e-10 * fmax(1.0, fabs(bref));
+    if constexpr (FN) {
+        if (fnr) {  // side 0: fn_min, side 1: -fn_max; the unit normal's selection norm
+            const double bd = fnb ? fnb[(sg > 0 ? WBC_FN_MIN : WBC_FN_MAX) + l] : __builtin_inf();
+            const bool ex = fabs(bd) < __builtin_inf();
+            b = ex ? sg * bd : 0.0;
+            nsel = 1.0;
+            tolv = ex ? 1e-10 * fmax(1.0, fabs(bd)) : -1.0;
+            if (!ex) {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) n[12 + j] = 0.0;
+            }
+        }
+    }
 }
 
 // C0[:, p] = J0^T n_p with J0 = blkdiag(I12, L^-T), in place: qdd part n, slot part L^-1 n_slot
@@ -3763,12 +3887,18 @@ static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing")
 // OBJ: as solve16's (the objective from the recovered 42-vector, one entry per lane)
 // DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot)
 // LM: as build_normal's (KernelArgs::lm is null here when the QP's row is not accepted)
-template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
     const int kap = (int)P.kappa;
-    const QpMap mp = make_map(kap);
+    QpMap mp = make_map(kap);
+    // FN: two force rows per stance leg after the swing rows (build_normal), at most 12 + 16 + 24 + 8 = 60
+    // constraints; the initial columns of lanes C0_LANES .. 59 go to eight lanes of LDS behind the scratch
+    // (SolveLdsFn::c0x), so QpScratch stays what every other kernel allocates
+    if constexpr (FN) mp.m += 2 * mp.ns;
+    [[maybe_unused]] double2 (*c0x)[C0X_LANES] = nullptr;
+    if constexpr (FN) c0x = reinterpret_cast<double2(*)[C0X_LANES]>(&s + 1);
     int status = WBC_QP_OK;
     int iters = 0;
     if (P.flags != 0.0) status = WBC_QP_NUMERIC;
@@ -3814,10 +3944,19 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
     double tolv = 0.0;  // violation tolerance of row p
     double sp0 = 0.0;  // slack at the unconstrained optimum x0
     bool is_eq = false, active = false;
-    const bool is_con = lane < mp.m;
+    bool is_con = lane < mp.m;
     {
         EST(a, rb, 5);
         double nsel;
+        if constexpr (FN) {
+            build_normal<true, true, true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN,
+                                           a.lm ? a.lm + (size_t)rb * WBC_LM_LEN : nullptr,
+                                           a.fn ? a.fn + (size_t)rb * WBC_FN_LEN : nullptr);
+            if (tolv < 0.0) {  // a force row without a finite bound: no constraint
+                is_con = false;
+                tolv = 1.0;
+            }
+        } else
         if constexpr (LM) build_normal<true, true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN,
                                                    a.lm ? a.lm + (size_t)rb * WBC_LM_LEN : nullptr);
         else if constexpr (CN) build_normal<true>(P, s.G, mp, pr, lane, cc, bp, is_eq, nsel, tolv, a.cn + (size_t)rb * WBC_CN_LEN);
@@ -3839,6 +3978,12 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
         if (lane < C0_LANES) {
 #pragma unroll
             for (int k = 0; k < NQ; k += 2) s.c0[k / 2][lane] = make_double2(cc[k], cc[k + 1]);
+        }
+        if constexpr (FN) {
+            if (lane >= C0_LANES && lane < C0_LANES + C0X_LANES) {
+#pragma unroll
+                for (int k = 0; k < NQ; k += 2) c0x[k / 2][lane - C0_LANES] = make_double2(cc[k], cc[k + 1]);
+            }
         }
     }
 
@@ -4051,6 +4196,7 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
         unsigned long long wm = ((int)Hh[H_WSKAP] == kap) ? ws : 0ull;
         wm &= ~((1ull << mp.neq) - 1ull);                        // inequalities only
         wm &= (mp.m >= 64) ? ~0ull : ((1ull << mp.m) - 1ull);
+        if constexpr (FN) wm &= __ballot(is_con);  // a force row whose bound became infinite leaves the warm set
         const int nw = __popcll(wm);
         if (nw > 0 && neq_added + nw <= NQ) {
             const bool mine = (wm >> lane) & 1ull;
@@ -4085,6 +4231,12 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
                         const double2 c = s.c0[k / 2][pl];
                         cc[k] = lane < C0_LANES ? c.x : 0.0;
                         cc[k + 1] = lane < C0_LANES ? c.y : 0.0;
+                        if constexpr (FN) {
+                            const bool xl = lane >= C0_LANES && lane < C0_LANES + C0X_LANES;
+                            const double2 cx = c0x[k / 2][xl ? lane - C0_LANES : 0];
+                            cc[k] = xl ? cx.x : cc[k];
+                            cc[k + 1] = xl ? cx.y : cc[k + 1];
+                        }
                     }
                     zero_rinv(s);
                     lds_sync();
@@ -4225,7 +4377,10 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int ak = bcast_i(act, k0 + j);
-                    const double2 c = s.c0[i >> 1][ak < 0 ? 0 : ak];
+                    double2 c = s.c0[i >> 1][ak < 0 ? 0 : (FN && ak >= C0_LANES) ? 0 : ak];
+                    if constexpr (FN) {
+                        if (ak >= C0_LANES) c = c0x[i >> 1][ak - C0_LANES];  // (uniform: ak is a broadcast)
+                    }
                     w4[j] = fma(bcast(u, k0 + j), (i & 1) ? c.y : c.x, w4[j]);
                 }
             }
@@ -4724,6 +4879,16 @@ struct SolveLds {
     Prob prob;
     QpScratch q;
 };
+// the force-bound instances' fallback solve (solve_phase<.., FN>): SolveLds and, right behind its scratch,
+// the initial columns of constraints C0_LANES .. C0_LANES + C0X_LANES - 1 (QpScratch::c0's layout)
+struct SolveLdsFn {
+    Prob prob;
+    QpScratch q;
+    double2 c0x[NQ / 2][C0X_LANES];
+};
+static_assert(offsetof(SolveLdsFn, q) == offsetof(SolveLds, q) &&
+              offsetof(SolveLdsFn, c0x) == offsetof(SolveLds, q) + sizeof(QpScratch), "c0x lies right behind the scratch");
+static_assert(sizeof(SolveLdsFn) <= sizeof(UpdLds), "the force-bound drain reuses the update scratch");
 
 // The one-kernel translation units (wbc_kernel_<unit>.hip) include this file under a macro that
 // keeps only their kernel and its launcher: WBC_STEP_INSTANCE (an instance of the default step, with
@@ -4835,7 +5000,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
-template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false>
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -4844,13 +5009,14 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
+constexpr bool fb_reads_fn(int tag) { return tag >= FB_STEP_FN; }  // the force-bound instances (KernelArgs::fn), limits instances too
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
 // the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, and lmd0 / lmd1 under a limits table
-constexpr bool fb_writes_dual(int tag) { return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || tag >= FB_STEP_LMD; }
+constexpr bool fb_writes_dual(int tag) { return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN); }
 constexpr bool fb_reads_lm(int tag) { return tag >= FB_STEP_LM; }  // the limits instances (KernelArgs::lm), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
@@ -4886,6 +5052,25 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             for (int c = 0; c < WBC_RP_LEN - 1; ++c) rv[c] = r[c];
             rp_apply(f.pv, ka->pv, rv, rp_bad_column(rv) >= 0);
         }
+        if constexpr (fb_reads_fn(TAG)) {
+            // the fallback QP's own limits row (there may be no limits table) and force-bound row, as below: a
+            // row the step does not accept (its robot is flagged) leaves no force row
+            const int q1 = __builtin_amdgcn_readlane(qp, seg * UPD_SUB);
+            f.lm = ka->lm;
+            if (ka->lm) {
+                const double* r = ka->lm + (size_t)q1 * WBC_LM_LEN;
+                double lv[WBC_LM_LEN];
+#pragma unroll
+                for (int c = 0; c < WBC_LM_LEN; ++c) lv[c] = r[c];
+                if (lm_bad_column(lv) >= 0) f.lm = nullptr;
+            }
+            const double* r = ka->fn + (size_t)q1 * WBC_FN_LEN;
+            double fv[WBC_FN_LEN];
+#pragma unroll
+            for (int c = 0; c < WBC_FN_LEN; ++c) fv[c] = r[c];
+            f.fn = fn_bad_column(fv) >= 0 ? nullptr : ka->fn;
+            solve_general_qp<true, false, false, true, true>(f, q1, *L);
+        } else {
         if constexpr (fb_reads_lm(TAG)) {
             // the fallback QP's own limits row: build_normal reads it where it stands; a row the step
             // does not accept (its robot is flagged) leaves the parameters' friction and max_torque
@@ -4896,6 +5081,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
             f.lm = lm_bad_column(lv) >= 0 ? nullptr : ka->lm;
         }
         solve_general_qp<fb_reads_cn(TAG), fb_writes_obj(TAG), fb_writes_dual(TAG), fb_reads_lm(TAG)>(f, __builtin_amdgcn_readlane(qp, seg * UPD_SUB), *L);
+        }
     }
 }
 // Workgroups are dispatched to the 8 XCDs round-robin (block b on XCD b % 8), each with its own
@@ -4940,8 +5126,14 @@ constexpr bool STEP_DU = false;
 // wbc_kernel_lmd1.hip) they are the duals instances of a wbc_step under a limits table (FB_STEP_LMD): a
 // DU stage behind a run-time test in lm0 / lm1 themselves would raise their fallback callee's frame from
 // bb0's 956 B to du0's 980 B.
-template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false>
+// FN (with LM, BB, CN and RP): the force-bound instances (wbc_kernel_fn0.hip, wbc_kernel_fn1.hip; DESIGN.md
+// 22): lane l >= 8 of a segment loads, with its inputs, its one bound of row qp of KernelArgs::fn, indexed as
+// the other rows are (lanes 8 + 2 leg and 9 + 2 leg hold fn_min and fn_max of one foot), and takes the unit
+// normal of that foot from the lane that holds its frame (lane 4 leg).  A null KernelArgs::lm leaves the
+// robot's own -+max_torque and friction in the limits' place.  A fallback callee of their own (FB_STEP_FN).
+template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false, bool FN = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
+    static_assert(!FN || (LM && !STEP_DU), "the force-bound instances are limits instances without duals");
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
     static_assert(!STEP_DU || (BB && !SONLY), "the duals instances are base-body instances of any mask mix");
@@ -5029,12 +5221,29 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     // torque rows 16 + lane and 32 + lane (side lane & 1: tau_min or tau_max; the second joint index is
     // valid in every lane, as solve16's k2) and the mu of its face's leg
     [[maybe_unused]] double lmv[3];
-    if constexpr (LM) {
+    if constexpr (LM && FN) {
+        if (a.lm) {  // (uniform: without a limits table the robot's own values stand, set below)
+            const double* r = a.lm + (size_t)qp * WBC_LM_LEN;
+            const int side = (lane & 1) ? WBC_LM_TAU_MAX : WBC_LM_TAU_MIN;
+            lmv[0] = r[side + (lane >> 1)];
+            lmv[1] = r[side + 8 + ((lane & 7) >> 1)];
+            lmv[2] = r[WBC_LM_FRICTION + (lane >> 2)];
+        } else {
+            lmv[0] = lmv[1] = lmv[2] = 0.0;
+        }
+    } else if constexpr (LM) {
         const double* r = a.lm + (size_t)qp * WBC_LM_LEN;
         const int side = (lane & 1) ? WBC_LM_TAU_MAX : WBC_LM_TAU_MIN;
         lmv[0] = r[side + (lane >> 1)];
         lmv[1] = r[side + 8 + ((lane & 7) >> 1)];
         lmv[2] = r[WBC_LM_FRICTION + (lane >> 2)];
+    }
+    // the lane's one force bound in the same batch: lane 8 + 2 leg + side holds fn_min[leg] (side 0) or
+    // fn_max[leg]; lanes < 8 load from a clamped valid address and hold "no row" (-inf / +inf by side)
+    [[maybe_unused]] double fnv[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (FN) {
+        const double w = a.fn[(size_t)qp * WBC_FN_LEN + (lane >= 8 ? (lane & 1) * 4 + ((lane - 8) >> 1) : 0)];
+        fnv[0] = lane >= 8 ? w : ((lane & 1) ? __builtin_inf() : -__builtin_inf());
     }
     // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy (the
     // limits instances: the model alone)
@@ -5067,6 +5276,22 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
         const bool bad = rp_bad_column(rpv) >= 0;
         rp_apply(ar.pv, a.pv, rpv, bad);
         if (bad) vin[0] = __builtin_nan("");
+        if constexpr (FN) {
+            if (!a.lm) {  // no limits table: the robot's own -+max_torque and friction (a valid row)
+                lmv[0] = lmv[1] = (lane & 1) ? ar.pv.max_torque : -ar.pv.max_torque;
+                lmv[2] = ar.pv.friction;
+            }
+            // the force-bound row's validity (fn_bad_column's pair rule: lanes 8 + 2 leg and 9 + 2 leg hold one
+            // foot's pair, lanes < 8 a valid one).  A row the step does not accept flags the robot as a bad
+            // parameter row does and leaves no force row
+            const double o = seg_shfl(fnv[0], lane ^ 1);
+            const bool hi = (lane & 1) != 0;
+            const bool fbad = seg_any<UPD_SUB>(fn_pair_bad(hi ? o : fnv[0], hi ? fnv[0] : o));
+            if (fbad) {
+                vin[0] = __builtin_nan("");
+                fnv[0] = hi ? __builtin_inf() : -__builtin_inf();
+            }
+        }
         if constexpr (LM) {
             // the row's validity (lm_bad_column's two entry rules on what the lanes hold: lanes 2 j and
             // 2 j + 1 hold tau_min and tau_max of joint j, and of joint 8 + j in the second slot; every mu is
@@ -5093,6 +5318,12 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
             cn_frame(cnm, fn, ft1, ft2);
 #pragma unroll
             for (int r = 0; r < 3; ++r) cnf[r] = cn_face_elem(fn, ft1, ft2, LM ? lmv[2] : ar.pv.friction, lane & 3, r);
+            if constexpr (FN) {
+                // the unit normal of the force row's leg (lane - 8) >> 1, from lane 4 leg, which holds that
+                // leg's frame (lanes < 8 read a lane of their segment and never use it)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) fnv[1 + r] = seg_shfl(fn[r], 4 * (((lane - 8) >> 1) & 3));
+            }
             if constexpr (BB) {
                 // every lane checks its robot's whole row (LDS broadcast reads); a row the step does not
                 // accept flags the robot as above, and the update reads the model's own base meanwhile:
@@ -5106,6 +5337,10 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
                 if (bbad) vin[0] = __builtin_nan("");
                 if (bbad) bbr = &L.model.base_mass;
             }
+            if constexpr (FN)
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU, LM, true>(
+                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr, lmv, fnv);
+            else
             solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU, LM>(
                 ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr, lmv);
         } else
@@ -5132,7 +5367,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(FN ? FB_STEP_FN : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -5306,7 +5541,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
-template <bool CN, bool OBJ, bool DU, bool LM>
+template <bool CN, bool OBJ, bool DU, bool LM, bool FN>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -5333,7 +5568,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
-template <bool CN, bool OBJ, bool DU, bool LM>
+template <bool CN, bool OBJ, bool DU, bool LM, bool FN>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -5360,7 +5595,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase<CN, OBJ, DU, LM>(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN, OBJ, DU, LM, FN>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5605,7 +5840,7 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 }  // namespace wbc
 
 #ifdef WBC_STEP_INSTANCE
-// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB[, LM]]>, in a translation unit
+// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB[, LM[, FN]]]>, in a translation unit
 // of its own so that its schedule can be chosen apart from the other kernels' (Makefile <UNIT>_KFLAGS):
 // the unit file names the launcher and the template arguments, the engine picks the launcher
 // (wbc_engine.cpp kStepLaunchers, wbc_layout.h step_instance).  The step in one launch: the update

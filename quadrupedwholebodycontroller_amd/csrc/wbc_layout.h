@@ -224,6 +224,14 @@ struct KernelArgs {
     // (Keep the block comment behind the declaration: tests/test_duals_cpu.py cuts lines at the line-comment
     // mark and expects dual to be the last that then ends in ';'.)
     const double* lm; /* [B][WBC_LM_LEN] */
+    // Per-foot normal-force bounds (wbc_set_force_bounds / wbc_bind_device_force_bounds): [batch][WBC_FN_LEN],
+    // row qp for QP qp (fn_min[4], fn_max[4]; fn_bad_column below); read only by the force-bound instances
+    // of the default step (wbc_kernel_fn0.hip, wbc_kernel_fn1.hip), which are limits, base-body,
+    // contact-normal and per-robot-parameter instances too: the engine points bb, cn and rp at tables of
+    // its own where none is in force, and a null lm leaves each robot's own -+max_torque and friction in
+    // the limits' place.  Last, so that no other argument's offset moves.  (The block comment stays behind
+    // the declaration, as lm's.)
+    const double* fn; /* [B][WBC_FN_LEN] */
 };
 
 // ---------------------------------------------------------------------------------------
@@ -255,12 +263,16 @@ WBC_HD inline int rp_bad_column(const double* r) {
 // BB (the base-body instances, a fifth template argument, false for the nine units above): no base-body
 // table.  LM (the limits instances, a sixth, false for every earlier unit): no limits table.  The other
 // forms take the flags in the template's order (a unit's WBC_STEP_INSTANCE).
-inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false, bool LM = false) {
+// FN (the force-bound instances, a seventh, false for every earlier unit): no force-bound table; such an
+// instance takes a null limits table (each robot's own -+max_torque and friction stand).
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false, bool LM = false,
+                              bool FN = false) {
     if (a.nwaves <= 0 || (a.stateful != 0) != (STF != 0)) return true;
     if (SONLY && (a.modes || a.qmap)) return true;
     if (RP && (a.modes || !a.rp)) return true;
     if (CN && !a.cn) return true;
     if (BB && !a.bb) return true;
+    if (FN) return !a.fn;
     return LM && !a.lm;
 }
 inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, const KernelArgs& a) {
@@ -268,6 +280,9 @@ inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, co
 }
 inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bool LM, const KernelArgs& a) {
     return step_args_refused(STF, SONLY, RP, CN, a, BB, LM);
+}
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bool LM, bool FN, const KernelArgs& a) {
+    return step_args_refused(STF, SONLY, RP, CN, a, BB, LM, FN);
 }
 // The default step's instances, one kernel unit each (wbc_kernel_<unit>.hip): per table in force
 // (none, parameters, parameters + normals; parameters + normals + base bodies in the second list
@@ -308,8 +323,20 @@ enum StepInstanceLM {
 #undef X
     STEP_EVERY_INSTANCE
 };
-constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false, bool lm = false) {
-    return lm ? (stateful ? (int)STEP_lm1 : (int)STEP_lm0)
+// The force-bound instances (KernelArgs::fn), in a fourth list whose values go on from
+// STEP_EVERY_INSTANCE: the launcher table has STEP_LAUNCHER_COUNT entries, built from the four lists in
+// this order.  fn wins over every other table; no stance-only unit, as the limits'.
+#define WBC_STEP_UNITS_FN(X) X(fn0) X(fn1)
+enum StepInstanceFN {
+    STEP_FN_FIRST_ = STEP_EVERY_INSTANCE - 1,
+#define X(unit) STEP_##unit,
+    WBC_STEP_UNITS_FN(X)
+#undef X
+    STEP_LAUNCHER_COUNT
+};
+constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false, bool lm = false, bool fn = false) {
+    return fn ? (stateful ? (int)STEP_fn1 : (int)STEP_fn0)
+         : lm ? (stateful ? (int)STEP_lm1 : (int)STEP_lm0)
          : bb ? (all_stance ? (int)STEP_bbs : stateful ? (int)STEP_bb1 : (int)STEP_bb0)
          : all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
          : stateful   ? (cn ? STEP_cn1 : rp ? STEP_rp1 : STEP_step1)
@@ -432,6 +459,21 @@ WBC_HD inline int lm_bad_column(const double* r) {
         if (!__builtin_isfinite(r[c])) return c;
         if (c >= WBC_LM_TAU_MAX && c < WBC_LM_FRICTION && lm_pair_bad(r[c - WBC_LM_TAU_MAX + WBC_LM_TAU_MIN], r[c])) return c;
         if (c >= WBC_LM_FRICTION && lm_mu_bad(r[c])) return c;
+    }
+    return -1;
+}
+// A force-bound row (wbc.h WBC_FN_*: fn_min[4], fn_max[4]) the step accepts: -1, or the first column that
+// fails: a NaN entry or fn_min = +inf at fn_min's column, fn_max = -inf or fn_min > fn_max at fn_max's
+// (equal bounds are valid; fn_min = -inf and fn_max = +inf mean no row).  One definition for the host's
+// validation (wbc_set_force_bounds) and the kernels' (a device-bound row): the kernels hold a foot's pair
+// in two neighbouring lanes and apply the pair rule, fn_pair_bad, to it.
+WBC_HD inline bool fn_lo_bad(double lo) { return !(lo < __builtin_inf()); }   // NaN or +inf
+WBC_HD inline bool fn_hi_bad(double hi) { return !(hi > -__builtin_inf()); }  // NaN or -inf
+WBC_HD inline bool fn_pair_bad(double lo, double hi) { return fn_lo_bad(lo) || fn_hi_bad(hi) || !(lo <= hi); }
+WBC_HD inline int fn_bad_column(const double* r) {
+    for (int c = 0; c < WBC_FN_LEN; ++c) {
+        if (c < WBC_FN_MAX && fn_lo_bad(r[c])) return c;
+        if (c >= WBC_FN_MAX && (r[c] != r[c] || fn_pair_bad(r[c - WBC_FN_MAX + WBC_FN_MIN], r[c]))) return c;
     }
     return -1;
 }

@@ -1,0 +1,336 @@
+"""CPU: the per-foot force-bound table (wbc_set_force_bounds, include/wbc.h) as far as it goes
+without a GPU: the oracle of tests/force_bounds_oracle.py against the limits oracle and the interior-point
+method, the Python table forms, wbc_layout.h's host functions in a sanitizer-built program, the compiler's
+resource report of the two new kernel units, and the new symbols of the built library."""
+import itertools
+import os
+import re
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import force_bounds_oracle as FO
+import limits_oracle as LO
+import qp_ipm as Q
+import wbc_np as W
+from quadrupedwholebodycontroller_amd import _capi, force_bounds_row, force_bounds_table, workloads
+from test_robot_params_cpu import _report
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
+INF = np.inf
+
+
+def test_names_follow_the_header():
+    hdr = open(os.path.join(ROOT, "include", "wbc.h")).read()
+    assert int(re.search(r"WBC_FN_LEN = (\d+)", hdr).group(1)) == _capi.FN_LEN == _capi.TABLES["force_bounds"] == FO.FN_LEN == 8
+    for name, col in (("MIN", _capi.FN_MIN), ("MAX", _capi.FN_MAX)):
+        assert int(re.search(rf"WBC_FN_{name} = (\d+)", hdr).group(1)) == col
+    for s in ("wbc_set_force_bounds", "wbc_bind_device_force_bounds", "wbc_get_force_bounds"):
+        assert s in _capi.C_API_SYMBOLS and re.search(rf"int32_t {s}\(", hdr)
+
+
+# 1 ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["stance_cold", "rl_random"])
+def test_default_row_is_the_limits_oracle(name):
+    """(-inf x 4, +inf x 4) gives LimitsWBC's default-row result bit for bit (the appended rows are dropped as
+    unbounded), and so does a row of bounds that never bind up to the solver's own working-set walk."""
+    B = 8
+    inp = getattr(workloads, name)(B, seed=91)
+    want = LO.run_batch(inp, np.tile(LO.default_row(), (B, 1)))
+    got = FO.run_batch(inp, np.tile(FO.NONE, (B, 1)))
+    for k in ("tau", "grf", "x", "status", "iters"):
+        assert np.array_equal(got[k], want[k]), (name, k)
+    assert np.array_equal(force_bounds_row(), FO.NONE) and np.array_equal(FO.row(), FO.NONE)
+
+
+# 2 ----------------------------------------------------------------------------------------------
+def test_seed7_sets_bind_and_the_infeasible_set_is_mixed():
+    """The preconditions of the GPU tests, so that they cannot pass on untouched QPs: every robot OK under
+    table(B, 7), a force bound tight (1e-7) on at least 40 of 64, 40 of 64 and 2 of 5 robots (53, 48 and 3
+    here), torques that move where it is; the unloaded feet carry nothing; fn_min = 500 N on every foot of
+    rl_random(16, 3) gives OK and INFEASIBLE robots (11 and 5 here)."""
+    got = {}
+    for name, least in (("stance_cold_64", 40), ("rl_random_64", 40), ("straight_5", 2)):
+        inp, t, res = FO.cold_set(name)
+        assert np.all(res["status"] == W.QP_OK), (name, res["status"])
+        got[name] = FO.tight_robots(res["grf"], res["status"], inp["contacts"], t)
+        assert got[name] >= least, got
+        plain = LO.run_batch(inp, np.tile(LO.default_row(), (len(t), 1)))
+        moved = int(np.sum(np.abs(plain["tau"] - res["tau"]).max(axis=1) > 1e-6))
+        assert moved >= least, (name, moved)
+        st = ((inp["contacts"][:, None] >> np.arange(4)) & 1) == 1
+        for b, l in FO.unloaded_feet(len(t)):
+            if st[b, l]:
+                assert np.abs(res["grf"][b].reshape(4, 3)[l]).max() <= 1e-12, (name, b, l)
+    print(got)
+    assert len(set(FO.cold_set("rl_random_61")[0]["contacts"].tolist())) == 16
+    _, _, res = FO.infeasible_set()
+    n_ok, n_inf = int(np.sum(res["status"] == W.QP_OK)), int(np.sum(res["status"] == W.QP_INFEASIBLE))
+    assert n_ok > 0 and n_inf > 0 and n_ok + n_inf == 16, res["status"]
+    _, _, res = FO.infeasible_set(2000.0)
+    assert int(np.sum(res["status"] == W.QP_INFEASIBLE)) >= 12, res["status"]
+
+
+@pytest.mark.parametrize("name", ["stance_cold_64", "rl_random_64", "straight_5"])
+def test_seed7_sets_agree_with_the_interior_point(name):
+    """The active-set solution satisfies the KKT conditions of the literal 42 x 74 QP (wbc_np.kkt_residuals:
+    primal violation at most 1e-10, stationarity at most 1e-8 absolute) and equals the interior point's x to 1e-8:
+    the bounds of tests/test_limits_cpu.py's check of its own sets."""
+    _, _, res = FO.cold_set(name)
+    worst = dict(viol=0.0, stat=0.0, ipm=0.0)
+    for b, c in enumerate(res["ctrl"]):
+        assert c.qp[2].shape == (74, 42)
+        viol, stat, _, _ = W.kkt_residuals(*c.qp, c.qp_solution)
+        worst["viol"], worst["stat"] = max(worst["viol"], viol), max(worst["stat"], stat)
+        if b % 4 == 0 or b % 8 == 3:
+            x, st = Q.solve(*c.qp)
+            assert st == W.QP_OK, b
+            worst["ipm"] = max(worst["ipm"], float(np.max(np.abs(x - c.qp_solution) / (1.0 + np.abs(x)))))
+    print(name, worst)
+    assert worst["viol"] <= 1e-10 and worst["stat"] <= 1e-8 and worst["ipm"] <= 1e-8, worst
+
+
+def test_ramp_tables():
+    """The load ramp's tables: valid rows, fn_max 0 on a leg's last stance cycle and on its touchdown cycle,
+    the base table away from the switch."""
+    seq = list(workloads.trot_sequence(8, steps=130, seed=2))[:130]
+    base = FO.table(8)
+    tabs = FO.ramp_tables(seq, base)
+    assert all(_capi.force_bounds_bad_column(r) < 0 for t in tabs for r in t)
+    assert np.array_equal(tabs[50], base, equal_nan=True) and np.array_equal(tabs[120], base, equal_nan=True)
+    assert np.all(tabs[99][:, [4, 6]] == 0.0) and np.all(tabs[100][:, [5, 7]] == 0.0)  # LH + RF lift off, LF + RH touch down
+    assert np.all(tabs[96][1:2, 4] == 0.5 * base[1, 4])
+
+
+# 3 ----------------------------------------------------------------------------------------------
+def test_python_table_forms():
+    B = 5
+    r = force_bounds_row(5.0, 90.0)
+    assert r.shape == (8,) and np.all(r[:4] == 5.0) and np.all(r[4:] == 90.0)
+    lo, hi = np.array([1.0, 2.0, 3.0, 4.0]), np.array([10.0, 20.0, INF, 40.0])
+    assert np.array_equal(force_bounds_row(lo, hi), np.concatenate([lo, hi]))
+    assert np.array_equal(force_bounds_row(fn_max=7.0), np.concatenate([np.full(4, -INF), np.full(4, 7.0)]))
+    with pytest.raises(ValueError, match="fn_min"):
+        force_bounds_row(np.zeros(3), 1.0)
+    base = np.tile(FO.NONE, (B, 1))
+    t = FO.table(B)
+    assert np.array_equal(force_bounds_table(B, base, t), t) and force_bounds_table(B, base, t).flags["C_CONTIGUOUS"]
+    assert np.array_equal(force_bounds_table(B, base, t[4]), np.tile(t[4], (B, 1)))
+    d = force_bounds_table(B, base, dict(fn_max=25.0))
+    assert np.all(d[:, 4:] == 25.0) and np.array_equal(d[:, :4], base[:, :4])
+    d = force_bounds_table(B, t, dict(fn_min=lo, fn_max=np.linspace(50.0, 90.0, B)))
+    assert np.array_equal(d[:, :4], np.tile(lo, (B, 1))) and np.array_equal(d[:, 4:], np.tile(np.linspace(50.0, 90.0, B)[:, None], (1, 4)))
+    d = force_bounds_table(B, base, dict(fn_min=t[:, :4], fn_max=t[:, 4:]))
+    assert np.array_equal(d, t)
+    for bad, msg in ((dict(force=1.0), "unknown force bound entries"), (dict(fn_max=np.zeros((B, 3))), "fn_max"),
+                     (np.zeros((B, 7)), "need shape")):
+        with pytest.raises(ValueError, match=msg):
+            force_bounds_table(B, base, bad)
+    # the rule the engine applies (wbc_layout.h fn_bad_column), restated
+    good = force_bounds_row(0.0, 100.0)
+    for col, v, at in ((1, np.nan, 1), (6, np.nan, 6), (2, INF, 2), (7, -INF, 7), (3, 101.0, 7), (5, -1.0, 5)):
+        e = good.copy()
+        e[col] = v
+        assert _capi.force_bounds_bad_column(e) == at, (col, v)
+    for col, v in ((0, -INF), (4, INF), (1, 100.0), (6, 0.0)):
+        e = good.copy()
+        e[col] = v
+        assert _capi.force_bounds_bad_column(e) == -1, (col, v)
+
+
+# 4 ----------------------------------------------------------------------------------------------
+PROG = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include "wbc_layout.h"
+int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "names")) {
+#define X(unit) std::printf("%d " #unit "\n", (int)wbc::STEP_##unit);
+        WBC_STEP_UNITS(X)
+        WBC_STEP_UNITS_BB(X)
+        WBC_STEP_UNITS_LM(X)
+        WBC_STEP_UNITS_FN(X)
+#undef X
+        std::printf("%d every\n%d launchers\n", (int)wbc::STEP_EVERY_INSTANCE, (int)wbc::STEP_LAUNCHER_COUNT);
+        return 0;
+    }
+    if (argc > 1 && !std::strcmp(argv[1], "rows")) {  // lines of 8 doubles: fn_bad_column on a heap block of exactly one row
+        for (;;) {
+            double* r = static_cast<double*>(std::malloc(WBC_FN_LEN * sizeof(double)));
+            bool ok = true;
+            for (int c = 0; c < WBC_FN_LEN && ok; ++c) {
+                char tok[64];
+                ok = std::scanf("%63s", tok) == 1;
+                if (ok) r[c] = std::strtod(tok, nullptr);
+            }
+            if (ok) {
+                int pair = -1;  // the pair rule the kernels apply, foot by foot
+                for (int l = WBC_NUM_LEGS - 1; l >= 0; --l)
+                    if (wbc::fn_pair_bad(r[WBC_FN_MIN + l], r[WBC_FN_MAX + l])) pair = l;
+                std::printf("%d %d\n", wbc::fn_bad_column(r), pair);
+            }
+            std::free(r);
+            if (!ok) break;
+        }
+        return 0;
+    }
+    if (argc > 1 && !std::strcmp(argv[1], "instance")) {
+        for (int i = 0; i < 128; ++i) {
+            const bool fn = i >> 6 & 1, lm = i >> 5 & 1, bb = i >> 4 & 1, cn = i >> 3 & 1, rp = i >> 2 & 1, as = i >> 1 & 1, st = i & 1;
+            std::printf("%d %d %d %d %d %d %d %d %d\n", (int)fn, (int)lm, (int)bb, (int)cn, (int)rp, (int)as, (int)st,
+                        (int)wbc::step_instance(cn, rp, as, st, bb, lm, fn), (int)wbc::step_instance(cn, rp, as, st, bb, lm));
+        }
+        return 0;
+    }
+    // "refused": lines of STF SONLY RP CN BB LM FN nwaves stateful modes qmap rp cn bb lm fn (pointers: 0 = null)
+    int stf, sonly, rp, cn, bb, lm, fn, nwaves, stateful, modes, qmap, prp, pcn, pbb, plm, pfn;
+    static const int32_t map[4] = {0, 0, 0, 0};
+    static const double tab[28] = {0};
+    while (std::scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", &stf, &sonly, &rp, &cn, &bb, &lm, &fn, &nwaves, &stateful,
+                      &modes, &qmap, &prp, &pcn, &pbb, &plm, &pfn) == 16) {
+        wbc::KernelArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.nwaves = nwaves;
+        a.stateful = stateful;
+        a.modes = modes;
+        a.qmap = qmap ? map : nullptr;
+        a.rp = prp ? tab : nullptr;
+        a.cn = pcn ? tab : nullptr;
+        a.bb = pbb ? tab : nullptr;
+        a.lm = plm ? tab : nullptr;
+        a.fn = pfn ? tab : nullptr;
+        std::printf("%d %d %d\n", (int)wbc::step_args_refused(stf, sonly != 0, rp != 0, cn != 0, a, bb != 0, lm != 0, fn != 0),
+                    (int)wbc::step_args_refused(stf, sonly != 0, rp != 0, cn != 0, bb != 0, lm != 0, fn != 0, a),
+                    (int)wbc::step_args_refused(stf, sonly != 0, rp != 0, cn != 0, a, bb != 0, lm != 0));
+    }
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def layout_bin(tmp_path_factory):
+    """The program above, built with the address and undefined-behaviour sanitizers when the host toolchain
+    links them (a stand-alone program: nothing is preloaded), else without."""
+    d = tmp_path_factory.mktemp("force_bounds")
+    src = d / "f.cpp"
+    src.write_text(PROG)
+    exe = d / "f"
+    cmd = ["g++", "-O1", "-g", "-Wall", "-Wno-unused-result", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+           str(src), "-o", str(exe)]
+    san = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True)
+    if san.returncode != 0 or subprocess.run([str(exe), "names"], capture_output=True).returncode != 0:
+        subprocess.run(cmd, check=True)
+    return str(exe)
+
+
+def _run(exe, mode, text=""):
+    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [l.split() for l in r.stdout.splitlines()]
+
+
+def test_fn_bad_column_host(layout_bin):
+    """wbc_layout.h's predicate over good rows and each invalid kind, equal to the Python one on all of them;
+    the pair rule the kernels apply fails on exactly the rows the column rule fails on."""
+    t = FO.table(16)
+    cases = [(r, -1) for r in t] + [(FO.NONE, -1), (force_bounds_row(0.0, 0.0), -1)]
+
+    def edit(*pairs):
+        r = force_bounds_row([1.0, 2.0, 3.0, 4.0], [50.0, 60.0, 70.0, 80.0])
+        for c, v in pairs:
+            r[c] = v
+        return r
+    cases += [(edit((c, np.nan)), c) for c in range(8)]
+    cases += [(edit((c, INF)), c) for c in range(4)] + [(edit((c, -INF)), c) for c in range(4, 8)]   # the wrong side
+    cases += [(edit((c, -INF)), -1) for c in range(4)] + [(edit((c, INF)), -1) for c in range(4, 8)]  # the right side
+    cases += [(edit((l, -INF), (4 + l, INF)), -1) for l in range(4)]
+    cases += [(edit((l, 5.0), (4 + l, 5.0)), -1) for l in (0, 3)]                            # equal bounds
+    cases += [(edit((l, 5.0), (4 + l, np.nextafter(5.0, 0.0))), 4 + l) for l in (0, 2, 3)]  # crossed by one ulp
+    cases += [(edit((l, 5.0), (4 + l, 4.0)), 4 + l) for l in (1, 3)]                         # crossed by one
+    cases += [(edit((2, 90.0)), 6), (edit((2, 90.0), (0, np.nan)), 0), (edit((2, 90.0), (5, np.nan)), 5)]  # the first failing column
+    cases += [(edit((0, -1e308), (4, 1e308)), -1), (edit((4, -3.0), (0, -5.0)), -1), (edit((7, -1.0)), 7)]
+    text = "".join(" ".join(repr(float(v)) for v in r) + "\n" for r, _ in cases)
+    got = [(int(l[0]), int(l[1])) for l in _run(layout_bin, "rows", text)]
+    assert len(got) == len(cases)
+    for (r, want), (g, pair) in zip(cases, got):
+        assert g == want == _capi.force_bounds_bad_column(r), (r, want, g)
+        assert (pair >= 0) == (want >= 0) and (want < 0 or pair == want % 4), (r, want, pair)
+
+
+def test_instance_choice_and_argument_check_with_fn(layout_bin):
+    """The new enumerators are 14 and 15 and a new count, 16, sizes the launcher table (STEP_EVERY_INSTANCE stays
+    14); step_instance with fn names fn0 / fn1 whatever else is set, and without it (the default) returns what it
+    returned; step_args_refused for an FN instance refuses what its bb instance refuses and a missing
+    force-bound table, and takes a missing limits table; the six-flag argument lists return what they returned."""
+    names = {n: int(i) for i, n in _run(layout_bin, "names")}
+    assert names.pop("every") == 14 and names.pop("launchers") == 16
+    assert [names[n] for n in ("fn0", "fn1")] == [14, 15] and sorted(names.values()) == list(range(16))
+    for fn, lm, bb, cn, rp, all_stance, stateful, got, without in ([int(v) for v in r] for r in _run(layout_bin, "instance")):
+        assert 0 <= without < 14
+        assert got == (names["fn1" if stateful else "fn0"] if fn else without), (fn, lm, bb, cn, rp, all_stance, stateful)
+    insts = [i for i in itertools.product((0, 1), repeat=7) if i[1] == 0]
+    args = [dict(nwaves=n, stateful=s, modes=m, qmap=0, rp=r, cn=c, bb=b, lm=l, fn=f)
+            for n, s, m, r, c, b, l, f in itertools.product((-1, 3), (0, 1), (0, 4), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1))]
+    text = "".join(" ".join(str(v) for v in (*inst, a["nwaves"], a["stateful"], a["modes"], a["qmap"], a["rp"], a["cn"], a["bb"],
+                                             a["lm"], a["fn"])) + "\n" for inst in insts for a in args)
+    got = iter([int(v) for v in l] for l in _run(layout_bin, "refused", text))
+    units = {(0, 0, 1, 1, 1, 1, 1): "fn0", (1, 0, 1, 1, 1, 1, 1): "fn1"}
+    seen = {u: [0, 0] for u in units.values()}
+    for inst in insts:
+        stf, sonly, rp, cn, bb, lm, fn = inst
+        for a in args:
+            trailing, ordered, six = next(got)
+            base = bool(a["nwaves"] <= 0 or bool(a["stateful"]) != bool(stf) or (rp and (a["modes"] or not a["rp"])) or
+                        (cn and not a["cn"]) or (bb and not a["bb"]))
+            assert six == int(base or bool(lm and not a["lm"])), (inst, a)
+            want = base or (not a["fn"] if fn else bool(lm and not a["lm"]))
+            assert trailing == ordered == int(want), (inst, a)
+            if inst in units:
+                seen[units[inst]][trailing] += 1
+    assert all(n_ok > 0 and n_ref > 0 for n_ok, n_ref in seen.values()), seen
+
+
+# 5 ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("unit,var,kernel,base,base_var", [
+    ("fn0", "FN0_KFLAGS", "wbc_update_solve_kernelILi0ELb0ELb1ELb1ELb1ELb1ELb1E", "lm0", "LM0_KFLAGS"),
+    ("fn1", "FN1_KFLAGS", "wbc_update_solve_kernelILi1ELb0ELb1ELb1ELb1ELb1ELb1E", "lm1", "LM1_KFLAGS"),
+])
+def test_new_units_resources(unit, var, kernel, base, base_var):
+    """The compiler's resource report of the force-bound units: at most 256 VGPRs, at most
+    40 960 B of LDS (four workgroups per CU), one wave per SIMD, no scratch instruction in the kernel's own body
+    (the report's scratch figure is the fallback callee's frame: it holds eight more initial columns' worth of
+    state than lm0's 956 B callee, and stays within 1 KiB).  Each unit holds its kernel and one drain_fallbacks,
+    and lm0 / lm1 name theirs as before (the seventh template flag is a suffix)."""
+    with ThreadPoolExecutor(2) as ex:
+        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+    assert len(new) == 1 and len(old) == 1, (list(new), list(old))
+    (name, rep), (oname, ref) = next(iter(new.items())), next(iter(old.items()))
+    assert kernel in name and kernel[:-5] in oname and kernel not in oname, (name, oname)
+    print(unit, rep, "against", base, ref)
+    assert rep["VGPRs"] <= 256 and rep["VGPRs"] + rep["AGPRs"] <= 512, rep
+    assert rep["LDS Size [bytes/block]"] <= 40960, rep
+    assert rep["Occupancy [waves/SIMD]"] == ref["Occupancy [waves/SIMD]"] == 1, (rep, ref)
+    assert rep["ScratchSize [bytes/lane]"] <= 1024, (rep, ref)
+    starts = [l.split(":")[0] for l in asm.split("\n") if re.match(r"^_Z\w+:", l)]
+    assert len(starts) == 2 and sum("drain_fallbacks" in n for n in starts) == 1, starts
+    # the kernel's own body (from its label to the end of its function) holds no scratch instruction
+    body = asm[asm.index("\n" + name + ":"):]
+    body = body[:body.index(".Lfunc_end")]
+    assert not re.search(r"^\s+scratch_", body, re.M), re.findall(r"^\s+scratch_\S+", body, re.M)[:4]
+
+
+def test_makefile_lists_and_library_symbols():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    ktu = re.search(r"^KTU := (.*)$", mk, re.M).group(1).split()
+    assert ktu[-2:] == ["fn0", "fn1"] and "KFLAGS_fn0 = $(FN0_KFLAGS)" in mk and "KFLAGS_fn1 = $(FN1_KFLAGS)" in mk
+    lib = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "libwbc_hip.so")
+    assert os.path.exists(lib), "libwbc_hip.so is not built (run __graft_entry__.build())"
+    syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for s in ("wbc_set_force_bounds", "wbc_bind_device_force_bounds", "wbc_get_force_bounds", "wbc_launch_update_solve_fn0",
+              "wbc_launch_update_solve_fn1"):
+        assert re.search(rf" T {s}$", syms, re.M), s
