@@ -10,7 +10,6 @@ validation's test is tests/test_gpu_base_body.py's."""
 import itertools
 import os
 import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -20,10 +19,9 @@ import base_body_oracle as BB
 import wbc_np as W
 import wbc_ref as R
 from quadrupedwholebodycontroller_amd import _capi, base_body_row, base_body_table, base_body_with_payload, workloads
-from test_robot_params_cpu import _report
+from unit_reports import build_host_program, report, run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
 KEYS = ("tau", "grf", "x", "status", "iters")
 
 
@@ -247,22 +245,7 @@ int main(int argc, char** argv) {
 def layout_bin(tmp_path_factory):
     """The program above, built with the address and undefined-behaviour sanitizers when the host
     toolchain links them (a stand-alone program: nothing is preloaded), else without."""
-    d = tmp_path_factory.mktemp("base_body")
-    src = d / "b.cpp"
-    src.write_text(PROG)
-    exe = d / "b"
-    cmd = ["g++", "-O1", "-g", "-Wall", "-Wno-unused-result", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           str(src), "-o", str(exe)]
-    san = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True)
-    if san.returncode != 0 or subprocess.run([str(exe), "names"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    return str(exe)
-
-
-def _run(exe, mode, text=""):
-    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return [l.split() for l in r.stdout.splitlines()]
+    return build_host_program(tmp_path_factory.mktemp("base_body"), "b", PROG)
 
 
 def test_bb_bad_entry_host(layout_bin):
@@ -293,7 +276,7 @@ def test_bb_bad_entry_host(layout_bin):
               (edit(mat=[[1.0, 2.0, 0.0], [2.0, 1.0, 0.0], [0.0, 0.0, 1.0]]), 8),
               (edit(mat=[[1.0, 0.0, 0.9], [0.0, 1.0, 0.9], [0.9, 0.9, 1.0]]), 12)]
     text = "".join(" ".join(repr(float(v)) for v in r) + "\n" for r, _ in cases)
-    got = [int(l[0]) for l in _run(layout_bin, "rows", text)]
+    got = [int(l[0]) for l in run_host_program(layout_bin, "rows", text)]
     assert len(got) == len(cases)
     for (r, want), g in zip(cases, got):
         assert g == want == _capi.base_body_bad_entry(r), (r, want, g)
@@ -303,10 +286,10 @@ def test_instance_choice_and_argument_check_with_bb(layout_bin):
     """step_instance with bb names the three new units, whose values go on from STEP_INSTANCES; without it
     (the default) it is what it was.  step_args_refused for the BB instances refuses what their cn
     instance refuses, and a missing base-body table; with BB false (the default) it is what it was."""
-    names = {n: int(i) for i, n in _run(layout_bin, "names")}
+    names = {n: int(i) for i, n in run_host_program(layout_bin, "names")}
     assert names.pop("count") == 9 and names.pop("all") == 12
     assert [names[n] for n in ("bb0", "bb1", "bbs")] == [9, 10, 11] and sorted(names.values()) == list(range(12))
-    for bb, cn, rp, all_stance, stateful, got, plain in ([int(v) for v in r] for r in _run(layout_bin, "instance")):
+    for bb, cn, rp, all_stance, stateful, got, plain in ([int(v) for v in r] for r in run_host_program(layout_bin, "instance")):
         assert 0 <= plain < 9
         if not bb:
             assert got == plain
@@ -319,7 +302,7 @@ def test_instance_choice_and_argument_check_with_bb(layout_bin):
             for n, s, m, q, r, c, b in itertools.product((-1, 0, 3), (0, 1, 2), (0, 4), (0, 1), (0, 1), (0, 1), (0, 1))]
     text = "".join(" ".join(str(v) for v in (*inst, a["nwaves"], a["stateful"], a["modes"], a["qmap"], a["rp"], a["cn"], a["bb"])) + "\n"
                    for inst in insts for a in args)
-    got = iter([int(v) for v in l] for l in _run(layout_bin, "refused", text))
+    got = iter([int(v) for v in l] for l in run_host_program(layout_bin, "refused", text))
     units = {(0, 0, 1, 1, 1): "bb0", (1, 0, 1, 1, 1): "bb1", (0, 1, 1, 1, 1): "bbs"}
     seen = {u: [0, 0] for u in units.values()}
     for inst in insts:
@@ -348,7 +331,7 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
     reported scratch size no larger than the base's (the fallback callee's frame), no scratch instruction
     in the kernel's own body, and the unit holding the kernel and one drain_fallbacks only."""
     with ThreadPoolExecutor(2) as ex:
-        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+        (new, asm), (old, _) = ex.map(lambda a: report(*a), [(unit, var), (base, base_var)])
     assert len(new) == 1 and len(old) == 1, (list(new), list(old))
     (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
     assert kernel in name, name

@@ -17,7 +17,7 @@ import contact_normals_oracle as CN
 import qp_ipm as Q
 import wbc_np as W
 from quadrupedwholebodycontroller_amd import _capi, contact_normal_table, workloads
-from test_robot_params_cpu import _report
+from unit_reports import report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("tau", "grf", "x", "status", "iters")
@@ -122,7 +122,7 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
     than the base's (the fallback callee's frame), no scratch instruction in the kernel's own body, and
     the unit holding the kernel and one drain_fallbacks only."""
     with ThreadPoolExecutor(2) as ex:
-        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+        (new, asm), (old, _) = ex.map(lambda a: report(*a), [(unit, var), (base, base_var)])
     assert len(new) == 1 and len(old) == 1, (list(new), list(old))
     (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
     assert kernel in name, name

@@ -18,7 +18,7 @@ import pytest
 import duals_oracle as D
 import wbc_np as W
 from quadrupedwholebodycontroller_amd import _capi, dual_rows
-from test_robot_params_cpu import _report
+from unit_reports import report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # The oracle's own residual: an fp64 least-squares fit of at most 12 + 18 multipliers to 42 equations whose
@@ -185,7 +185,7 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
     flags = lambda v: re.search(rf"^{v} := (.*)$", mk, re.M).group(1).split()
     assert flags(var) == flags(base_var)
     with ThreadPoolExecutor(2) as ex:
-        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+        (new, asm), (old, _) = ex.map(lambda a: report(*a), [(unit, var), (base, base_var)])
     assert len(new) == 1 and len(old) == 1, (list(new), list(old))
     (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
     assert kernel in name, name

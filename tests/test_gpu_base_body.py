@@ -5,7 +5,7 @@ wbc_kernel_bbs.hip for all-stance stateless steps).
 
 The checkers are tests/base_body_oracle.py's: the C and numpy oracles given one model per robot.  The
 tables are base_body_oracle.payload_rows(B): a point payload of up to 60 % of the base mass somewhere
-on the trunk; the input sets are those of tests/test_gpu_robot_params.py (seed 91; the straight-leg set
+on the trunk; the input sets are tests/table_steps.py's inputs(name, B) (seed 91; the straight-leg set
 from seed 81), on which the C oracle returns WBC_QP_OK for every robot under these payloads; bounds are
 tests/margins.py's."""
 import ctypes as C
@@ -18,15 +18,17 @@ import pytest
 import base_body_oracle as BB
 import contact_normals_oracle as CN
 import stateful_sequences as S
+import table_steps as T
 import wbc_ref as R
 from quadrupedwholebodycontroller_amd import (COLD, DEBUG, FUSED, GROUP, QP_NUMERIC, QP_OK, RESIDENT, SPLIT, STATELESS, Engine,
                                               WbcError, split_debug, workloads)
-from test_gpu_robot_params import assert_identical, check_against_oracle, inputs, load, row_dict
-from test_gpu_robot_params import table as rp_table
+from table_steps import (ERR_ARG, ERR_STATE, assert_identical, check_against_c_oracles, inputs, last_error, load, moved,
+                         row_dict)
+from table_steps import table as rp_table
 
 pytestmark = pytest.mark.gpu
 
-ERR_ARG, ERR_STATE = -1, -3
+BODY = T.Table("base_body")
 _ORACLE = {}
 
 
@@ -40,23 +42,7 @@ def oracle(name, B):
 
 
 def run(inp, rows=None, t=None, nrm=None, flags=STATELESS):
-    e = Engine(len(inp["contacts"]))
-    load(e, inp)
-    if t is not None:
-        e.set_robot_params(t)
-    if nrm is not None:
-        e.set_contact_normals(nrm)
-    if rows is not None:
-        e.set_base_body(rows)
-    e.step(flags)
-    out = e.outputs()
-    e.close()
-    return out
-
-
-def moved(a, b, by=1e-3):
-    """Robots whose tau differs by more than `by` N m."""
-    return int((np.abs(a["tau"] - b["tau"]).max(axis=1) > by).sum())
+    return T.run(inp, flags, robot_params=t, contact_normals=nrm, base_body=rows)
 
 
 # 1 ----------------------------------------------------------------------------------------------
@@ -74,7 +60,7 @@ def test_payload_matches_oracle_cold(name, B):
     assert np.all(lit["status"] == QP_OK), lit["status"]
     bent = np.nonzero(np.arange(B) % 5 != 0)[0] if name == "straight" else None
     out = run(inp, rows)
-    check_against_oracle(out, lit, red, name, bent)
+    check_against_c_oracles(out, lit, red, name, bent)
     if name == "straight":
         fb = np.arange(0, B, 5)
         d = np.abs(run(inp)["tau"][fb] - out["tau"][fb]).max(axis=1)
@@ -88,7 +74,7 @@ def test_payload_matches_oracle_cold(name, B):
     e.bind_device_inputs(contacts=masks.data_ptr())
     for flags in (STATELESS | GROUP, STATELESS):
         e.step(flags)
-        check_against_oracle(e.outputs(), lit, red, f"{name}, device masks, flags {flags}", bent)
+        check_against_c_oracles(e.outputs(), lit, red, f"{name}, device masks, flags {flags}", bent)
     e.close()
 
 
@@ -180,13 +166,8 @@ def test_all_three_tables_at_once():
     inp, rows, t, nrm = inputs("rl_random", B), BB.payload_rows(B), rp_table(B), CN.normals(B, 5, 0.35)
     ref = BB.np_run_batch(inp, rows, [row_dict(t[b]) for b in range(B)], CN.SlopedWBC, [dict(normals=nrm[b]) for b in range(B)])
     out = run(inp, rows, t, nrm)
-    assert np.array_equal(out["status"], ref["status"]), (out["status"], ref["status"])
-    ok = np.nonzero(ref["status"] == QP_OK)[0]
-    assert len(ok) >= B - 4, ref["status"]
-    for b in ok:
-        assert M.close(out["tau"][b], ref["tau"][b], M.TAU, "tau"), b
-        assert M.close(out["grf"][b], ref["grf"][b], M.GRF, "grf"), b
-        assert M.close(out["x"][b], ref["x"][b], M.X, "x"), b
+    assert np.sum(ref["status"] == QP_OK) >= B - 4, ref["status"]
+    T.check_against_oracle(out, ref, "three tables")
 
 
 # 6 ----------------------------------------------------------------------------------------------
@@ -194,17 +175,7 @@ def test_a_robot_depends_on_its_own_row_only():
     """A permuted batch gives permuted bits, and changing one robot's row changes that robot alone."""
     B = 61
     inp, rows, _, _ = oracle("rl_random", B)
-    out = run(inp, rows)
-    perm = np.random.default_rng(4).permutation(B)
-    pin = {k: np.ascontiguousarray(v[perm]) for k, v in inp.items()}
-    assert_identical(run(pin, rows[perm]), out, idx_b=perm, what="permuted")
-    b = 17
-    r2 = rows.copy()
-    r2[b] = BB.payload_rows(B, seed=12)[b]
-    out2 = run(inp, r2)
-    others = np.arange(B) != b
-    assert_identical(out2, out, idx_a=others, idx_b=others, what="other robots")
-    assert np.abs(out2["tau"][b] - out["tau"][b]).max() > 1e-3
+    T.own_row_only(BODY, inp, rows, 17, BB.payload_rows(B, seed=12)[17])
 
 
 # 7 ----------------------------------------------------------------------------------------------
@@ -252,9 +223,7 @@ def test_device_bound_table_with_invalid_rows():
     """NaN, zero mass, an asymmetric and an indefinite inertia in a device-bound table: those robots get
     WBC_QP_NUMERIC and zeros, every other robot the bits of a run without the bad rows (stateless, and
     the first stateful step of a fresh engine)."""
-    torch = pytest.importorskip("torch")
-    B = 61
-    inp, rows, _, _ = oracle("rl_random", B)
+    inp, rows, _, _ = oracle("rl_random", 61)
     I = rows[0, 4:13].reshape(3, 3)
     asym = I.copy()
     asym[0, 1] += 1e-6 * np.trace(I)
@@ -264,24 +233,7 @@ def test_device_bound_table_with_invalid_rows():
     bad[30, 4:13] = asym.ravel()
     bad[44, 4:13] = np.diag([1.0, -1.0, 1.0]).ravel()
     bad[60, 12] = np.inf
-    rows_bad = np.array([3, 17, 30, 44, 60])
-    others = np.setdiff1d(np.arange(B), rows_bad)
-    d = torch.from_numpy(np.ascontiguousarray(bad)).cuda()
-    torch.cuda.synchronize()
-    for flags in (STATELESS, 0):
-        e = Engine(B)
-        load(e, inp)
-        e.bind_device_base_body(d)
-        e.step(flags)
-        out = e.outputs()
-        got = e.base_body()
-        assert np.array_equal(got[:, :13], bad[:, :13], equal_nan=True) and not got[:, 13].any()
-        e.close()
-        ref = run(inp, rows, flags=flags)
-        assert np.all(out["status"][rows_bad] == QP_NUMERIC), out["status"][rows_bad]
-        for k in ("tau", "grf", "x"):
-            assert not out[k][rows_bad].any(), k
-        assert_identical(out, ref, idx_a=others, idx_b=others, what=("others", flags))
+    T.device_bound_invalid_rows(BODY, inp, rows, bad, np.array([3, 17, 30, 44, 60]))  # (the reserved column reads back as 0)
 
 
 # 8b ---------------------------------------------------------------------------------------------
@@ -345,30 +297,12 @@ def test_device_bound_row_invalid_for_one_cycle():
 
 
 # 9 ----------------------------------------------------------------------------------------------
-BB_IS = "a per-robot base body table is in force (default wbc_step only; clear it with wbc_set_base_body(h, NULL))"
-BB_WITH = " with a per-robot base body table in force ({}; clear it with wbc_set_base_body(h, NULL))"
-REFUSALS = {
-    "update": "wbc_update: " + BB_IS,
-    "solve": "wbc_solve: " + BB_IS,
-    "step_split": "wbc_step: WBC_SPLIT" + BB_WITH.format("default form only"),
-    "step_fused": "wbc_step: WBC_FUSED" + BB_WITH.format("default form only"),
-    "step_modes": "wbc_step_modes: " + BB_IS,
-    "cycle_split": "wbc_cycle: WBC_SPLIT" + BB_WITH.format("plain cycle only"),
-    "cycle_fused": "wbc_cycle: WBC_FUSED" + BB_WITH.format("plain cycle only"),
-    "cycle_resident": "wbc_cycle: WBC_RESIDENT" + BB_WITH.format("plain cycle only"),
-}
+REFUSALS = T.refusal_texts("a per-robot base body table is in force", "a per-robot base body table in force",
+                           "clear it with wbc_set_base_body(h, NULL)")
 assert REFUSALS["cycle_resident"] == ("wbc_cycle: WBC_RESIDENT with a per-robot base body table in force (plain cycle only; "
                                       "clear it with wbc_set_base_body(h, NULL))")
 assert REFUSALS["step_modes"] == ("wbc_step_modes: a per-robot base body table is in force (default wbc_step only; clear it with "
                                   "wbc_set_base_body(h, NULL))")
-
-
-def _cycle(e, inp, flags):
-    return e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
-
-
-def last_error(e):
-    return e.lib.wbc_last_error().decode()
 
 
 def test_host_validation_refusals_cycle_and_clearing():
@@ -395,22 +329,9 @@ def test_host_validation_refusals_cycle_and_clearing():
     e.step(STATELESS)
     out = e.outputs()
     assert moved(out, run(inp)) == B
-    assert_identical(_cycle(e, inp, STATELESS), out, what="cycle")
+    assert_identical(T.cycle(e, inp, STATELESS), out, what="cycle")
     # refusals, letter for letter
-    calls = {
-        "update": lambda: e.update(STATELESS),
-        "solve": lambda: e.solve(STATELESS),
-        "step_split": lambda: e.step(STATELESS | SPLIT),
-        "step_fused": lambda: e.step(STATELESS | FUSED),
-        "cycle_split": lambda: _cycle(e, inp, STATELESS | SPLIT),
-        "cycle_fused": lambda: _cycle(e, inp, STATELESS | FUSED),
-        "cycle_resident": lambda: _cycle(e, inp, STATELESS | RESIDENT),
-    }
-    for name, call in calls.items():
-        with pytest.raises(WbcError) as ei:
-            call()
-        assert last_error(e) == REFUSALS[name], name
-        assert f"({ERR_STATE})" in str(ei.value), name
+    T.refused_forms(e, inp, REFUSALS)
     # the other tables are named first, as before
     e.set_contact_normals(np.array([0.0, 0.0, 1.0]))
     with pytest.raises(WbcError):
@@ -423,23 +344,11 @@ def test_host_validation_refusals_cycle_and_clearing():
     with pytest.raises(WbcError) as ei:
         e.step_modes(STATELESS)
     assert last_error(e) == REFUSALS["step_modes"] and f"({ERR_STATE})" in str(ei.value)
-    e.set_modes(None)
-    # cleared: every form runs again and matches an engine that never had the table
+    # cleared: wbc_step_modes and every other form run again and match an engine that never had the table
     e.set_base_body(None)
     assert np.array_equal(e.base_body(), np.tile(BB.default_row(), (B, 1)))
     f = Engine(B)
-    load(f, inp)
-    for flags in (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, 0):
-        load(e, inp)
-        e.step(flags)
-        f.step(flags)
-        assert_identical(e.outputs(), f.outputs(), what=("cleared", flags))
-    for eng in (e, f):
-        eng.update(STATELESS)
-        eng.solve(STATELESS)
-    assert_identical(e.outputs(), f.outputs(), what="cleared, update + solve")
-    for flags in (STATELESS, STATELESS | RESIDENT):
-        assert_identical(_cycle(e, inp, flags), _cycle(f, inp, flags), what=("cleared cycle", flags))
+    T.cleared_matches_fresh(e, f, inp, (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, 0), (STATELESS, STATELESS | RESIDENT))
     for eng in (e, f):
         eng.close()
 

@@ -13,14 +13,14 @@ import margins as M
 import pytest
 
 import contact_normals_oracle as CN
-from quadrupedwholebodycontroller_amd import (COLD, DEBUG, FUSED, GROUP, NO_X, QP_NUMERIC, QP_OK, RESIDENT, SPLIT, STATELESS,
-                                              TIMED, Engine, WbcError, workloads)
-from test_gpu_robot_params import row_dict, table
+import table_steps as T
+from quadrupedwholebodycontroller_amd import (COLD, DEBUG, FUSED, GROUP, NO_X, QP_OK, RESIDENT, SPLIT, STATELESS, TIMED, Engine,
+                                              WbcError, workloads)
+from table_steps import ERR_ARG, ERR_STATE, assert_identical, check_against_oracle, last_error, load, row_dict, table
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("tau", "grf", "x", "status", "iters")
-ERR_ARG, ERR_STATE = -1, -3
+NORMALS = T.Table("contact_normals")
 SEED, NSEED, TILT = 11, 5, 0.35
 
 
@@ -44,42 +44,13 @@ def oracle(name, B, with_table=False):
     return _ORACLE[key]
 
 
-def load(e, inp):
-    e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-    e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-
-
 def run(inp, nrm=None, t=None, flags=STATELESS):
-    e = Engine(len(inp["contacts"]))
-    load(e, inp)
-    if t is not None:
-        e.set_robot_params(t)
-    if nrm is not None:
-        e.set_contact_normals(nrm)
-    e.step(flags)
-    out = e.outputs()
-    e.close()
-    return out
-
-
-def check_against_oracle(out, ref, what):
-    assert np.array_equal(out["status"], ref["status"]), (what, out["status"], ref["status"])
-    for b in np.nonzero(ref["status"] == QP_OK)[0]:
-        assert M.close(out["tau"][b], ref["tau"][b], M.TAU, "tau"), (what, b)
-        assert M.close(out["grf"][b], ref["grf"][b], M.GRF, "grf"), (what, b)
-        assert M.close(out["x"][b], ref["x"][b], M.X, "x"), (what, b)
-
-
-def assert_identical(a, b, idx_a=None, idx_b=None, what=""):
-    for k in KEYS:
-        va = a[k] if idx_a is None else a[k][idx_a]
-        vb = b[k] if idx_b is None else b[k][idx_b]
-        assert np.array_equal(va, vb), (what, k)
+    return T.run(inp, flags, robot_params=t, contact_normals=nrm)
 
 
 def moved(a, b):
     """Robots whose tau differs by more than 1e-6 N m."""
-    return int((np.abs(a["tau"] - b["tau"]).max(axis=1) > 1e-6).sum())
+    return T.moved(a, b, by=1e-6)
 
 
 # 1 ----------------------------------------------------------------------------------------------
@@ -158,17 +129,8 @@ def test_a_robot_depends_on_its_own_row_only():
     """A permuted batch gives permuted bits, and changing one robot's row changes that robot alone."""
     B = 61
     inp, nrm, _, _ = oracle("rl_random", B)
-    out = run(inp, nrm)
-    perm = np.random.default_rng(4).permutation(B)
-    pin = {k: np.ascontiguousarray(v[perm]) for k, v in inp.items()}
-    assert_identical(run(pin, nrm[perm]), out, idx_b=perm, what="permuted")
     b = int(np.nonzero(inp["contacts"] == 15)[0][0])
-    n2 = nrm.copy()
-    n2[b] = CN.normals(1, 99, 0.5)[0]
-    out2 = run(inp, n2)
-    others = np.arange(B) != b
-    assert_identical(out2, out, idx_a=others, idx_b=others, what="other robots")
-    assert np.abs(out2["tau"][b] - out["tau"][b]).max() > 1e-6
+    T.own_row_only(NORMALS, inp, nrm, b, CN.normals(1, 99, 0.5)[0], by=1e-6)
 
 
 # 5 ----------------------------------------------------------------------------------------------
@@ -216,43 +178,22 @@ def test_stateful_trot_with_the_normals_swapped():
 def test_device_bound_table_with_invalid_feet():
     """NaN, |m| = 0, m_z < 0 and a 70 degree tilt in a device-bound table: those robots get
     WBC_QP_NUMERIC and zeros, every other robot the bits of a run without the bad rows."""
-    torch = pytest.importorskip("torch")
     B = 61
     inp, nrm, _, _ = oracle("rl_random", B)
-    good = run(inp, nrm)
     t70 = np.deg2rad(70.0)
     bad = {3: (0, [np.nan, 0.0, 1.0]), 17: (2, [0.0, 0.0, 0.0]), 30: (1, [0.1, 0.0, -1.0]),
            44: (3, [np.sin(t70), 0.0, np.cos(t70)]), 60: (0, [0.0, np.inf, 1.0])}
     n2 = nrm.copy()
     for b, (l, m) in bad.items():
         n2[b, l] = m
-    d = torch.from_numpy(np.ascontiguousarray(n2.reshape(B, 12))).cuda()
-    torch.cuda.synchronize()
-    for flags in (STATELESS, 0):
-        e = Engine(B)
-        load(e, inp)
-        e.bind_device_contact_normals(d)
-        e.step(flags)
-        out = e.outputs()
-        assert np.array_equal(e.contact_normals(), n2.reshape(B, 12), equal_nan=True)
-        e.close()
-        ref = good if flags else None
-        if ref is None:  # the first stateful step of a fresh engine against the same with good rows
-            e = Engine(B)
-            load(e, inp)
-            e.set_contact_normals(nrm)
-            e.step(0)
-            ref = e.outputs()
-            e.close()
-        rows = np.array(sorted(bad))
-        assert np.all(out["status"][rows] == QP_NUMERIC), out["status"][rows]
-        for k in ("tau", "grf", "x"):
-            assert not out[k][rows].any(), k
-        others = np.setdiff1d(np.arange(B), rows)
-        assert_identical(out, ref, idx_a=others, idx_b=others, what=("others", flags))
+    T.device_bound_invalid_rows(NORMALS, inp, nrm, n2.reshape(B, 12), np.array(sorted(bad)))
 
 
 # 7 ----------------------------------------------------------------------------------------------
+REFUSALS = T.refusal_texts("contact normals are in force", "contact normals in force", "clear them with wbc_set_contact_normals(h, NULL)")
+assert REFUSALS["solve"] == "wbc_solve: contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))"
+
+
 def test_host_validation_refusals_cycle_and_clearing():
     B = 8
     inp = inputs("rl_random", B)
@@ -278,51 +219,30 @@ def test_host_validation_refusals_cycle_and_clearing():
     e.step(STATELESS)
     out = e.outputs()
     assert moved(out, run(inp)) >= 1
-    cyc = e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], STATELESS)
-    assert_identical(cyc, out, what="cycle")
+    assert_identical(T.cycle(e, inp, STATELESS), out, what="cycle")
     for flags in (STATELESS | DEBUG, STATELESS | NO_X, STATELESS | TIMED):
         e.step(flags)
         o = e.outputs()
         for k in ("tau", "grf", "status", "iters"):
             assert np.array_equal(o[k], out[k]), (flags, k)
-    # refusals, each naming its call or flag
-    calls = [("wbc_update", lambda: e.update(STATELESS)), ("wbc_solve", lambda: e.solve(STATELESS)),
-             ("WBC_SPLIT", lambda: e.step(STATELESS | SPLIT)), ("WBC_FUSED", lambda: e.step(STATELESS | FUSED)),
-             ("WBC_SPLIT", lambda: e.cycle(*[inp[k] for k in ("base_pose", "nu", "qj", "ref", "contacts", "switching")], STATELESS | SPLIT)),
-             ("WBC_FUSED", lambda: e.cycle(*[inp[k] for k in ("base_pose", "nu", "qj", "ref", "contacts", "switching")], STATELESS | FUSED)),
-             ("WBC_RESIDENT", lambda: e.cycle(*[inp[k] for k in ("base_pose", "nu", "qj", "ref", "contacts", "switching")], STATELESS | RESIDENT))]
-    for name, call in calls:
-        with pytest.raises(WbcError) as ei:
-            call()
-        assert name in str(ei.value) and "contact normals" in str(ei.value), (name, str(ei.value))
-        assert e.lib.wbc_last_error().decode() and str(ERR_STATE) in str(ei.value), str(ei.value)
+    # refusals, letter for letter
+    T.refused_forms(e, inp, REFUSALS)
     e.set_contact_normals(None)
     e.set_modes([15, 5])
     e.set_contact_normals(nrm)
     with pytest.raises(WbcError) as ei:
         e.step_modes(STATELESS)
-    assert "wbc_step_modes" in str(ei.value) and "contact normals" in str(ei.value), str(ei.value)
-    e.set_modes(None)
-    # cleared: every form runs again and matches an engine that never had normals
+    assert last_error(e) == REFUSALS["step_modes"] and f"({ERR_STATE})" in str(ei.value)
+    # cleared: wbc_step_modes and every other form run again and match an engine that never had normals
     e.set_contact_normals(None)
     assert np.array_equal(e.contact_normals(), np.tile([0.0, 0.0, 1.0], (B, 4)))
     f = Engine(B)
-    load(f, inp)
-    for flags in (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, 0):
-        load(e, inp)
-        e.step(flags)
-        f.step(flags)
-        assert_identical(e.outputs(), f.outputs(), what=("cleared", flags))
-    for eng in (e, f):
-        eng.update(STATELESS)
-        eng.solve(STATELESS)
-    assert_identical(e.outputs(), f.outputs(), what="cleared, update + solve")
-    small = {k: v[:4] for k, v in inp.items()}
+    T.cleared_matches_fresh(e, f, inp, (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, 0), ())
+    small = T.take(inp, slice(0, 4))
     e4, f4 = Engine(4), Engine(4)
     e4.set_contact_normals(nrm[:4])
     e4.set_contact_normals(None)
-    args = [small[k] for k in ("base_pose", "nu", "qj", "ref", "contacts", "switching")]
     for flags in (STATELESS, STATELESS | RESIDENT):
-        assert_identical(e4.cycle(*args, flags), f4.cycle(*args, flags), what=("cleared cycle", flags))
+        assert_identical(T.cycle(e4, small, flags), T.cycle(f4, small, flags), what=("cleared cycle", flags))
     for eng in (e, f, e4, f4):
         eng.close()

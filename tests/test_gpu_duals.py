@@ -20,37 +20,28 @@ import duals_oracle as D
 import wbc_np as W
 from quadrupedwholebodycontroller_amd import (COLD, DEBUG, DUALS, FUSED, GROUP, NO_X, QP_OK, RESIDENT, SPLIT, STATELESS, TIMED,
                                               Engine, WbcError, default_params, dual_rows, workloads)
-from test_gpu_robot_params import assert_identical, load
-from test_gpu_robot_params import table as rp_table
+import table_steps as T
+from table_steps import ERR_ARG, ERR_STATE, assert_identical, last_error, load
+from table_steps import table as rp_table
 
 pytestmark = pytest.mark.gpu
 
-ERR_ARG, ERR_STATE = -1, -3
-KEYS = ("tau", "grf", "x", "status", "iters")
 
-
-def engine(B, over=None):
+def params(over=None):
     p = default_params()
     for k, v in (over or {}).items():
         setattr(p, k, v)
-    return Engine(B, params=p)
+    return p
+
+
+def engine(B, over=None):
+    return Engine(B, params=params(over))
 
 
 def run(inp, flags, over=None, t=None, nrm=None, rows=None, duals=True):
-    """One step on a fresh engine: (outputs, duals or None)."""
-    e = engine(len(inp["contacts"]), over)
-    load(e, inp)
-    if t is not None:
-        e.set_robot_params(t)
-    if nrm is not None:
-        e.set_contact_normals(nrm)
-    if rows is not None:
-        e.set_base_body(rows)
-    e.step(flags)
-    out = e.outputs()
-    d = e.duals() if duals else None
-    e.close()
-    return out, d
+    """One step on a fresh engine: (outputs, duals or None).  Every call that reads the duals passes WBC_DUALS in `flags`."""
+    out = T.run(inp, flags, duals, params=params(over), robot_params=t, contact_normals=nrm, base_body=rows)
+    return out, out.pop("dual", None)
 
 
 def certify(name, cs, out, d, contacts, what=""):
@@ -282,8 +273,7 @@ def test_a_robot_depends_on_its_own_inputs_only():
     inp, over, _ = D.cold_set("rl_random_45")
     out, d = run(inp, STATELESS | DUALS, over)
     perm = np.random.default_rng(4).permutation(45)
-    pin = {k: np.ascontiguousarray(v[perm]) for k, v in inp.items()}
-    pout, pd = run(pin, STATELESS | DUALS, over)
+    pout, pd = run(T.take(inp, perm), STATELESS | DUALS, over)
     assert_identical(pout, out, idx_b=perm, what="permuted")
     assert np.array_equal(pd, d[perm])
 
@@ -312,10 +302,6 @@ def test_device_pointer_holds_the_duals():
 
 
 # 7 ----------------------------------------------------------------------------------------------
-def last_error(e):
-    return e.lib.wbc_last_error().decode()
-
-
 def test_errors():
     """WBC_DUALS is WBC_ERR_ARG on wbc_update, wbc_solve, wbc_cycle and wbc_step_modes, and on wbc_step with
     WBC_SPLIT, WBC_FUSED or WBC_RESIDENT; the getters are WBC_ERR_STATE before a flagged step and after an
@@ -328,11 +314,10 @@ def test_errors():
         with pytest.raises(WbcError) as ei:
             get()
         assert f"({ERR_STATE})" in str(ei.value) and "did not carry WBC_DUALS" in last_error(e)
-    cyc = lambda flags: e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
     calls = {
         "wbc_update": lambda: e.update(STATELESS | DUALS),
         "wbc_solve": lambda: e.solve(STATELESS | DUALS),
-        "wbc_cycle": lambda: cyc(STATELESS | DUALS),
+        "wbc_cycle": lambda: T.cycle(e, inp, STATELESS | DUALS),
         "wbc_step split": lambda: e.step(STATELESS | DUALS | SPLIT),
         "wbc_step fused": lambda: e.step(STATELESS | DUALS | FUSED),
         "wbc_step resident": lambda: e.step(STATELESS | DUALS | RESIDENT),

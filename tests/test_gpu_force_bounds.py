@@ -16,42 +16,25 @@ import base_body_oracle as BB
 import contact_normals_oracle as CN
 import force_bounds_oracle as FO
 import limits_oracle as LO
-from quadrupedwholebodycontroller_amd import (COLD, DUALS, FUSED, GROUP, NO_X, QP_INFEASIBLE, QP_NUMERIC, QP_OK, RESIDENT, SPLIT,
-                                              STATELESS, Engine, WbcError, force_bounds_row, workloads)
-from test_gpu_robot_params import assert_identical, inputs, load, row_dict
-from test_gpu_robot_params import table as rp_table
+import table_steps as T
+from quadrupedwholebodycontroller_amd import (COLD, DUALS, FUSED, GROUP, NO_X, QP_INFEASIBLE, QP_OK, RESIDENT, SPLIT, STATELESS,
+                                              Engine, WbcError, force_bounds_row, workloads)
+from table_steps import ERR_ARG, ERR_STATE, assert_identical, inputs, last_error, load, row_dict
+from table_steps import table as rp_table
 
 pytestmark = pytest.mark.gpu
 
-ERR_ARG, ERR_STATE = -1, -3
+FN = T.Table("force_bounds")
 INF = np.inf
 
 
 def run(inp, fn=None, lm=None, t=None, nrm=None, rows=None, flags=STATELESS):
-    e = Engine(len(inp["contacts"]))
-    load(e, inp)
-    if t is not None:
-        e.set_robot_params(t)
-    if nrm is not None:
-        e.set_contact_normals(nrm)
-    if rows is not None:
-        e.set_base_body(rows)
-    if lm is not None:
-        e.set_limits(lm)
-    if fn is not None:
-        e.set_force_bounds(fn)
-    e.step(flags)
-    out = e.outputs()
-    e.close()
-    return out
+    return T.run(inp, flags, robot_params=t, contact_normals=nrm, base_body=rows, limits=lm, force_bounds=fn)
 
 
 def check_against_oracle(out, ref, what):
-    assert np.array_equal(out["status"], ref["status"]), (what, out["status"], ref["status"])
-    for b in np.nonzero(ref["status"] == QP_OK)[0]:
-        assert M.close(out["tau"][b], ref["tau"][b], M.TAU, "tau"), (what, b)
-        assert M.close(out["grf"][b], ref["grf"][b], M.GRF, "grf"), (what, b)
-        assert M.close(out["x"][b], ref["x"][b], M.X, "x"), (what, b)
+    """table_steps.check_against_oracle, and zero outputs on the robots the oracle did not solve."""
+    T.check_against_oracle(out, ref, what)
     for k in ("tau", "grf", "x"):
         assert not out[k][ref["status"] != QP_OK].any(), (what, k)
 
@@ -189,18 +172,9 @@ def test_all_five_tables_at_once():
 def test_a_robot_depends_on_its_own_row_only():
     """A permuted batch gives permuted bits, and changing one robot's row changes that robot alone."""
     inp, t, _ = FO.cold_set("rl_random_61")
-    B = len(inp["contacts"])
-    out = run(inp, t)
-    perm = np.random.default_rng(4).permutation(B)
-    pin = {k: np.ascontiguousarray(v[perm]) for k, v in inp.items()}
-    assert_identical(run(pin, t[perm]), out, idx_b=perm, what="permuted")
     b = 20  # (mask with stance feet, both bounds finite)
-    t2 = t.copy()
-    t2[b] = force_bounds_row(0.0, 20.0)
-    out2 = run(inp, t2)
-    others = np.arange(B) != b
-    assert_identical(out2, out, idx_a=others, idx_b=others, what="other robots")
-    assert inp["contacts"][b] != 0 and np.abs(out2["tau"][b] - out["tau"][b]).max() > 1e-3
+    assert inp["contacts"][b] != 0
+    T.own_row_only(FN, inp, t, b, force_bounds_row(0.0, 20.0))
 
 
 # 7 ----------------------------------------------------------------------------------------------
@@ -267,9 +241,7 @@ def test_device_bound_table_with_invalid_rows():
     """NaN, fn_min > fn_max by 1 and by one ulp, fn_min = +inf and fn_max = -inf in a device-bound table: those
     robots get WBC_QP_NUMERIC and zeros, every other robot the bits of a run without the bad rows (stateless
     and the first stateful step); an unbind restores the host table."""
-    torch = pytest.importorskip("torch")
     inp, t, _ = FO.cold_set("rl_random_61")
-    B = len(inp["contacts"])
     bad = t.copy()
     bad[4, 5] = np.nan
     bad[13, 2] = np.nan
@@ -277,57 +249,18 @@ def test_device_bound_table_with_invalid_rows():
     bad[30, 3], bad[30, 7] = 1.0, np.nextafter(1.0, 0.0)
     bad[44, 0] = INF
     bad[60, 6] = -INF
-    rows_bad = np.array([4, 13, 17, 30, 44, 60])
-    others = np.setdiff1d(np.arange(B), rows_bad)
-    d = torch.from_numpy(np.ascontiguousarray(bad)).cuda()
-    torch.cuda.synchronize()
-    for flags in (STATELESS, 0):
-        ref = run(inp, t, flags=flags)
-        e = Engine(B)
-        load(e, inp)
-        host = FO.table(B, seed=8)
-        e.set_force_bounds(host)
-        e.bind_device_force_bounds(d)
-        e.step(flags)
-        out = e.outputs()
-        assert np.array_equal(e.force_bounds(), bad, equal_nan=True)
-        assert np.all(out["status"][rows_bad] == QP_NUMERIC), out["status"][rows_bad]
-        for k in ("tau", "grf", "x"):
-            assert not out[k][rows_bad].any(), k
-        assert_identical(out, ref, idx_a=others, idx_b=others, what=("others", flags))
-        e.bind_device_force_bounds(None)
-        assert np.array_equal(e.force_bounds(), host)
-        if flags == STATELESS:
-            e.step(flags)
-            assert_identical(e.outputs(), run(inp, host, flags=flags), what="unbound: the host table")
-        e.close()
+    T.device_bound_invalid_rows(FN, inp, t, bad, np.array([4, 13, 17, 30, 44, 60]), host=FO.table(len(t), seed=8))
 
 
 # 9 ----------------------------------------------------------------------------------------------
-FN_IS = "per-foot force bounds are in force (default wbc_step only; clear them with wbc_set_force_bounds(h, NULL))"
-FN_WITH = " with per-foot force bounds in force ({}; clear them with wbc_set_force_bounds(h, NULL))"
 REFUSALS = {
-    "update": "wbc_update: " + FN_IS,
-    "solve": "wbc_solve: " + FN_IS,
-    "step_modes": "wbc_step_modes: " + FN_IS,
-    "step_split": "wbc_step: WBC_SPLIT" + FN_WITH.format("default form only"),
-    "step_fused": "wbc_step: WBC_FUSED" + FN_WITH.format("default form only"),
-    "cycle_split": "wbc_cycle: WBC_SPLIT" + FN_WITH.format("plain cycle only"),
-    "cycle_fused": "wbc_cycle: WBC_FUSED" + FN_WITH.format("plain cycle only"),
-    "cycle_resident": "wbc_cycle: WBC_RESIDENT" + FN_WITH.format("plain cycle only"),
+    **T.refusal_texts("per-foot force bounds are in force", "per-foot force bounds in force",
+                      "clear them with wbc_set_force_bounds(h, NULL)"),
     "step_duals": ("wbc_step: WBC_DUALS with per-foot force bounds in force (the 40 multipliers have no entry for a force "
                    "row; clear them with wbc_set_force_bounds(h, NULL))"),
 }
 assert REFUSALS["update"] == ("wbc_update: per-foot force bounds are in force (default wbc_step only; clear them with "
                               "wbc_set_force_bounds(h, NULL))")
-
-
-def _cycle(e, inp, flags):
-    return e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
-
-
-def last_error(e):
-    return e.lib.wbc_last_error().decode()
 
 
 def test_host_validation_refusals_cycle_and_clearing():
@@ -360,26 +293,12 @@ def test_host_validation_refusals_cycle_and_clearing():
     e.step(STATELESS)
     out = e.outputs()
     assert np.abs(out["tau"] - run(inp)["tau"]).max() > 1e-3
-    assert_identical(_cycle(e, inp, STATELESS), out, what="cycle")
+    assert_identical(T.cycle(e, inp, STATELESS), out, what="cycle")
     e.step(STATELESS | NO_X)
     for k in ("tau", "grf", "status", "iters"):
         assert np.array_equal(e.outputs()[k], out[k]), k
     # refusals, letter for letter
-    calls = {
-        "update": lambda: e.update(STATELESS),
-        "solve": lambda: e.solve(STATELESS),
-        "step_split": lambda: e.step(STATELESS | SPLIT),
-        "step_fused": lambda: e.step(STATELESS | FUSED),
-        "cycle_split": lambda: _cycle(e, inp, STATELESS | SPLIT),
-        "cycle_fused": lambda: _cycle(e, inp, STATELESS | FUSED),
-        "cycle_resident": lambda: _cycle(e, inp, STATELESS | RESIDENT),
-        "step_duals": lambda: e.step(STATELESS | DUALS),
-    }
-    for name, call in calls.items():
-        with pytest.raises(WbcError) as ei:
-            call()
-        assert last_error(e) == REFUSALS[name], name
-        assert f"({ERR_STATE})" in str(ei.value), name
+    T.refused_forms(e, inp, REFUSALS, extra={"step_duals": lambda: e.step(STATELESS | DUALS)})
     # the other tables are named first, as before
     e.set_limits(LO.table(B))
     with pytest.raises(WbcError):
@@ -394,27 +313,10 @@ def test_host_validation_refusals_cycle_and_clearing():
     assert last_error(e) == REFUSALS["step_modes"] and f"({ERR_STATE})" in str(ei.value)
     # cleared: every refused form runs again and matches an engine that never had the table
     e.set_force_bounds(None)
-    f = Engine(B)
-    f.set_modes([15, 5])
-    for eng in (e, f):
-        eng.set_state(inp["base_pose"][:2], inp["nu"][:2], inp["qj"][:2])
-        eng.set_reference(inp["ref"][:2], inp["contacts"][:2], inp["switching"][:2])
-        eng.step_modes(STATELESS)
-    assert_identical(e.outputs(), f.outputs(), what="cleared, step_modes")
-    for eng in (e, f):
-        eng.set_modes(None)
     assert np.array_equal(e.force_bounds(), np.tile(FO.NONE, (B, 1)))
-    for flags in (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, STATELESS | DUALS, 0):
-        for eng in (e, f):
-            load(eng, inp)
-            eng.step(flags)
-        assert_identical(e.outputs(), f.outputs(), what=("cleared", flags))
-    for eng in (e, f):
-        eng.update(STATELESS)
-        eng.solve(STATELESS)
-    assert_identical(e.outputs(), f.outputs(), what="cleared, update + solve")
-    for flags in (STATELESS, STATELESS | SPLIT, STATELESS | RESIDENT):
-        assert_identical(_cycle(e, inp, flags), _cycle(f, inp, flags), what=("cleared cycle", flags))
+    f = Engine(B)
+    T.cleared_matches_fresh(e, f, inp, (STATELESS, STATELESS | SPLIT, STATELESS | FUSED, STATELESS | DUALS, 0),
+                            (STATELESS, STATELESS | SPLIT, STATELESS | RESIDENT))
     for eng in (e, f):
         eng.close()
 

@@ -20,8 +20,9 @@ import pytest
 import wbc_np as W
 from quadrupedwholebodycontroller_amd import (BEST, NO_X, OBJECTIVE, SPLIT, STATELESS, Engine, WbcError, default_params,
                                               workloads)
+from table_steps import ERR_ARG, ERR_STATE, last_error
 from test_gpu_modes import per_row, replicated
-from test_gpu_tables_and_bindings import ERR_ARG, ERR_STATE, REFUSALS, last_error
+from test_gpu_tables_and_bindings import REFUSALS
 
 pytestmark = pytest.mark.gpu
 

@@ -5,7 +5,7 @@ stateful, wbc_kernel_rps.hip for all-stance stateless steps).
 
 The checker is the C oracle run robot by robot under that robot's row (wbc_ref.run_batch /
 wbc_ref.Robot take every field as an override); all bounds are tests/margins.py's.  The fixed tables
-are numpy.random.default_rng(seed), uniform per column over RANGES; under the rng(7) table the oracle
+are tests/table_steps.py's table(B, seed): numpy.random.default_rng(seed), uniform per column over RANGES; under the rng(7) table the oracle
 returns WBC_QP_OK for 64 of 64 robots on each cold input set used here."""
 import ctypes as C
 
@@ -14,39 +14,14 @@ import numpy as np
 import margins as M
 import pytest
 
+import table_steps as T
 import wbc_ref as R
-from quadrupedwholebodycontroller_amd import (COLD, FUSED, GROUP, QP_NUMERIC, QP_OK, RESIDENT, ROBOT_PARAM_NAMES, SPLIT,
-                                              STATELESS, Engine, WbcError, default_params, workloads)
+from quadrupedwholebodycontroller_amd import (COLD, FUSED, GROUP, QP_NUMERIC, QP_OK, RESIDENT, ROBOT_PARAM_NAMES, SPLIT, STATELESS,
+                                              Engine, WbcError, default_params, workloads)
+from table_steps import (ERR_ARG, ERR_STATE, KEYS, assert_identical, check_against_c_oracles, inputs, last_error, load, row_dict,
+                         table, take)
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("tau", "grf", "x", "status", "iters")
-RANGES = dict(friction=(0.35, 1.5), max_torque=(15, 80), kp=(3000, 9000), kp_z=(5000, 15000), kd=(900, 2700), ki=(0, 50),
-              kp_swing=(125, 500), kd_swing=(10, 40), slack_weight=(100, 10000))
-ERR_ARG, ERR_STATE = -1, -3
-
-
-def table(B, seed=7):
-    g = np.random.default_rng(seed)
-    t = np.zeros((B, 10))
-    for c, name in enumerate(ROBOT_PARAM_NAMES):
-        t[:, c] = g.uniform(*RANGES[name], B)
-    return t
-
-
-def row_dict(row):
-    return {n: float(row[c]) for c, n in enumerate(ROBOT_PARAM_NAMES)}
-
-
-def take(inp, idx):
-    return {k: np.ascontiguousarray(v[idx]) for k, v in inp.items()}
-
-
-def inputs(name, B):
-    if name == "straight":
-        return workloads.straight_legs(workloads.stance_cold(B, seed=81))
-    return getattr(workloads, name)(B, seed=91)
-
 
 _ORACLE = {}
 
@@ -64,40 +39,8 @@ def oracle(name, B, seed=7):
     return _ORACLE[key]
 
 
-def load(e, inp):
-    e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-    e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-
-
-def run(inp, t=None, flags=STATELESS, params=None):
-    e = Engine(len(inp["contacts"]), params=params)
-    load(e, inp)
-    if t is not None:
-        e.set_robot_params(t)
-    e.step(flags)
-    out = e.outputs()
-    e.close()
-    return out
-
-
-def check_against_oracle(out, lit, red, what, iters_rows=None):
-    B = len(lit["status"])
-    assert np.array_equal(out["status"], lit["status"]), (what, out["status"], lit["status"])
-    ok = np.nonzero(lit["status"] == QP_OK)[0]
-    assert len(ok) >= B - 4, (what, len(ok))
-    for b in ok:
-        assert M.close(out["tau"][b], lit["tau"][b], M.TAU, "tau"), (what, b)
-        assert M.close(out["grf"][b], lit["grf"][b], M.GRF, "grf"), (what, b)
-        assert M.close(out["x"][b], lit["x"][b], M.X, "x"), (what, b)
-    rows = np.arange(B) if iters_rows is None else iters_rows
-    assert np.array_equal(out["iters"][rows], red["iters"][rows]), (what, out["iters"][rows], red["iters"][rows])
-
-
-def assert_identical(a, b, idx_a=None, idx_b=None, what=""):
-    for k in KEYS:
-        va = a[k] if idx_a is None else a[k][idx_a]
-        vb = b[k] if idx_b is None else b[k][idx_b]
-        assert np.array_equal(va, vb), (what, k)
+def run(inp, t=None, flags=STATELESS):
+    return T.run(inp, flags, robot_params=t)
 
 
 # 1 ----------------------------------------------------------------------------------------------
@@ -110,7 +53,7 @@ def test_heterogeneous_table_matches_oracle_cold(name):
     inp, t, lit, red = oracle(name, B)
     out = run(inp, t)
     bent = np.nonzero(np.arange(B) % 5 != 0)[0] if name == "straight" else None  # straight_legs: every 5th robot
-    check_against_oracle(out, lit, red, name, bent)
+    check_against_c_oracles(out, lit, red, name, bent)
     if name == "straight":  # the fallback ran under the robot's own row: the engine-wide values give other torques
         plain = run(inp)
         fb = np.arange(0, B, 5)
@@ -126,7 +69,7 @@ def test_ragged_batches_and_device_masks(B):
     torch = pytest.importorskip("torch")
     inp, t, lit, red = oracle("rl_random", B)
     out = run(inp, t)
-    check_against_oracle(out, lit, red, f"B={B}")
+    check_against_c_oracles(out, lit, red, f"B={B}")
     e = Engine(B)
     load(e, inp)
     e.set_robot_params(t)
@@ -135,7 +78,7 @@ def test_ragged_batches_and_device_masks(B):
     for flags in (STATELESS | GROUP, STATELESS):  # grouped by the device map, and unmapped (mixed waves)
         e.step(flags)
         dev = e.outputs()
-        check_against_oracle(dev, lit, red, f"B={B} device masks, flags {flags}")
+        check_against_c_oracles(dev, lit, red, f"B={B} device masks, flags {flags}")
     e.close()
 
 
@@ -245,61 +188,33 @@ def test_device_bound_table_and_invalid_rows():
 
 
 # 7 ----------------------------------------------------------------------------------------------
-def _cycle(e, inp, flags):
-    return e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
+REFUSALS = T.refusal_texts("a per-robot parameter table is in force", "a per-robot parameter table in force",
+                           "clear it with wbc_set_robot_params(h, NULL)")
+assert REFUSALS["step_fused"] == ("wbc_step: WBC_FUSED with a per-robot parameter table in force (default form only; clear it "
+                                  "with wbc_set_robot_params(h, NULL))")
 
 
 def test_refusals_and_plain_cycle():
     B = 4
     inp, t = workloads.rl_random(B, seed=91), table(B)
-    modes = [15, 5]
-    calls = {
-        "wbc_update": lambda e: e.update(STATELESS),
-        "wbc_solve": lambda e: e.solve(STATELESS),
-        "WBC_SPLIT": lambda e: e.step(STATELESS | SPLIT),
-        "WBC_FUSED": lambda e: e.step(STATELESS | FUSED),
-        "WBC_RESIDENT": lambda e: _cycle(e, inp, STATELESS | RESIDENT),
-    }
-    e, ref = Engine(B), Engine(B)
+    e = Engine(B)
     load(e, inp)
-    load(ref, inp)
     e.set_robot_params(t)
-    for name, call in calls.items():
-        with pytest.raises(WbcError) as ei:
-            call(e)
-        assert f"({ERR_STATE})" in str(ei.value) and name in str(ei.value), (name, str(ei.value))
+    T.refused_forms(e, inp, REFUSALS)
     # plain cycle under the table is the step under the table
     e.step(STATELESS)
     want = e.outputs()
-    assert_identical(_cycle(e, inp, STATELESS), want, what="plain cycle")
+    assert_identical(T.cycle(e, inp, STATELESS), want, what="plain cycle")
     assert not np.array_equal(want["tau"], run(inp)["tau"])
     # mode hypotheses: wbc_step_modes is refused while the table is in force
-    e.set_modes(modes)
+    e.set_modes([15, 5])
     with pytest.raises(WbcError) as ei:
         e.step_modes(STATELESS)
-    assert f"({ERR_STATE})" in str(ei.value) and "wbc_step_modes" in str(ei.value), str(ei.value)
+    assert last_error(e) == REFUSALS["step_modes"] and f"({ERR_STATE})" in str(ei.value)
     # the table cleared: every form runs again and matches an engine that never had one
     e.set_robot_params(None)
-    ref.set_modes(modes)
-    st = take(inp, slice(0, B // len(modes)))
-    load(e, st)
-    load(ref, st)
-    e.step_modes(STATELESS)
-    ref.step_modes(STATELESS)
-    assert_identical(e.outputs(), ref.outputs(), what="step_modes after clearing")
-    e.set_modes(None)
-    ref.set_modes(None)
-    load(e, inp)
-    load(ref, inp)
-    e.update(STATELESS)
-    ref.update(STATELESS)
-    calls["wbc_update"] = lambda x: (x.update(STATELESS), x.solve(STATELESS))
-    for name, call in calls.items():
-        got, exp = call(e), call(ref)
-        if name == "WBC_RESIDENT":
-            assert_identical(got, exp, what=name)
-        else:
-            assert_identical(e.outputs(), ref.outputs(), what=name + " after clearing")
+    ref = Engine(B)
+    T.cleared_matches_fresh(e, ref, inp, (STATELESS | SPLIT, STATELESS | FUSED), (STATELESS | RESIDENT,))
     e.close()
     ref.close()
 

@@ -30,7 +30,7 @@ import contact_normals_oracle as CN
 import stateful_sequences as S
 import wbc_ref as R
 from quadrupedwholebodycontroller_amd import COLD, DEBUG, QP_INFEASIBLE, QP_OK, SPLIT, Engine, split_debug
-from test_gpu_robot_params import row_dict, table
+from table_steps import row_dict, table
 
 pytestmark = pytest.mark.gpu
 
@@ -278,7 +278,7 @@ def test_mixed_forms():
 @pytest.mark.parametrize("latch", [True, False], ids=["latched", "unlatched"])
 def test_table(latch):
     """The per-robot-parameter stateful instance (wbc_kernel_rp1.hip) off the trot, under
-    test_gpu_robot_params.table(8, 11), robot b against Robot(**row_dict(row b)): status, tau, x and grf
+    table_steps.table(8, 11), robot b against Robot(**row_dict(row b)): status, tau, x and grf
     against LITERAL, iters against REDUCED.  grf is held to margins.STATEFUL_TABLE_GRF, not margins.GRF:
     under this table the run has QPs (robot 0, cycle 355: one stance leg carrying 0.14 N on the edge of
     its friction cone beside joint accelerations of 300) where one ulp on the inputs moves the oracle's

@@ -14,63 +14,23 @@ import numpy as np
 import pytest
 
 import contact_normals_oracle as CN
-from quadrupedwholebodycontroller_amd import FUSED, RESIDENT, SPLIT, STATELESS, Engine, WbcError, workloads
-from test_gpu_robot_params import table as rp_table
+import table_steps as T
+from quadrupedwholebodycontroller_amd import RESIDENT, SPLIT, STATELESS, Engine, WbcError, workloads
+from table_steps import ERR_ARG, ERR_STATE, KEYS, assert_identical, cycle, last_error, load
+from table_steps import table as rp_table
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("tau", "grf", "x", "status", "iters")
-ERR_ARG, ERR_STATE = -1, -3
-
-
-def load(e, inp):
-    e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-    e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-
-
-def cycle(e, inp, flags):
-    return e.cycle(inp["base_pose"], inp["nu"], inp["qj"], inp["ref"], inp["contacts"], inp["switching"], flags)
-
-
-def assert_identical(a, b, what=""):
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), (what, k)
 
 
 def cn_table(B, seed):
     return np.ascontiguousarray(CN.normals(B, seed, 0.35).reshape(B, 12))
 
 
-def last_error(e):
-    return e.lib.wbc_last_error().decode()
-
-
 # --- refusal texts ----------------------------------------------------------------------------------
-RP_IS = "a per-robot parameter table is in force (default wbc_step only; clear it with wbc_set_robot_params(h, NULL))"
-CN_ARE = "contact normals are in force (default wbc_step only; clear them with wbc_set_contact_normals(h, NULL))"
-RP_WITH = " with a per-robot parameter table in force ({}; clear it with wbc_set_robot_params(h, NULL))"
-CN_WITH = " with contact normals in force ({}; clear them with wbc_set_contact_normals(h, NULL))"
 REFUSALS = {
-    "rp": {
-        "update": "wbc_update: " + RP_IS,
-        "solve": "wbc_solve: " + RP_IS,
-        "step_split": "wbc_step: WBC_SPLIT" + RP_WITH.format("default form only"),
-        "step_fused": "wbc_step: WBC_FUSED" + RP_WITH.format("default form only"),
-        "step_modes": "wbc_step_modes: " + RP_IS,
-        "cycle_split": "wbc_cycle: WBC_SPLIT" + RP_WITH.format("plain cycle only"),
-        "cycle_fused": "wbc_cycle: WBC_FUSED" + RP_WITH.format("plain cycle only"),
-        "cycle_resident": "wbc_cycle: WBC_RESIDENT" + RP_WITH.format("plain cycle only"),
-    },
-    "cn": {
-        "update": "wbc_update: " + CN_ARE,
-        "solve": "wbc_solve: " + CN_ARE,
-        "step_split": "wbc_step: WBC_SPLIT" + CN_WITH.format("default form only"),
-        "step_fused": "wbc_step: WBC_FUSED" + CN_WITH.format("default form only"),
-        "step_modes": "wbc_step_modes: " + CN_ARE,
-        "cycle_split": "wbc_cycle: WBC_SPLIT" + CN_WITH.format("plain cycle only"),
-        "cycle_fused": "wbc_cycle: WBC_FUSED" + CN_WITH.format("plain cycle only"),
-        "cycle_resident": "wbc_cycle: WBC_RESIDENT" + CN_WITH.format("plain cycle only"),
-    },
+    "rp": T.refusal_texts("a per-robot parameter table is in force", "a per-robot parameter table in force",
+                          "clear it with wbc_set_robot_params(h, NULL)"),
+    "cn": T.refusal_texts("contact normals are in force", "contact normals in force", "clear them with wbc_set_contact_normals(h, NULL)"),
 }
 # written out once in full, so that the pieces above are checked against a whole sentence too
 assert REFUSALS["rp"]["cycle_resident"] == ("wbc_cycle: WBC_RESIDENT with a per-robot parameter table in force (plain cycle only; "
@@ -92,20 +52,7 @@ def test_refusal_texts(tables):
     if tables in ("cn", "both"):
         e.set_contact_normals(cn_table(B, 5))
     want = REFUSALS["cn" if tables == "cn" else "rp"]
-    calls = {
-        "update": lambda: e.update(STATELESS),
-        "solve": lambda: e.solve(STATELESS),
-        "step_split": lambda: e.step(STATELESS | SPLIT),
-        "step_fused": lambda: e.step(STATELESS | FUSED),
-        "cycle_split": lambda: cycle(e, inp, STATELESS | SPLIT),
-        "cycle_fused": lambda: cycle(e, inp, STATELESS | FUSED),
-        "cycle_resident": lambda: cycle(e, inp, STATELESS | RESIDENT),
-    }
-    for name, call in calls.items():
-        with pytest.raises(WbcError) as ei:
-            call()
-        assert last_error(e) == want[name], name
-        assert f"({ERR_STATE})" in str(ei.value), name
+    T.refused_forms(e, inp, want)
     e.set_modes([15, 5])
     with pytest.raises(WbcError) as ei:
         e.step_modes(STATELESS)
@@ -146,24 +93,7 @@ def test_validation_texts():
 
 
 # --- table precedence ---------------------------------------------------------------------------------
-class Table:
-    """The calls of one of the two tables, and three tables of it."""
-
-    def __init__(self, kind, B):
-        self.kind = kind
-        if kind == "rp":
-            self.tables = [rp_table(B, seed) for seed in (7, 8, 9)]
-        else:
-            self.tables = [cn_table(B, seed) for seed in (5, 6, 7)]
-
-    def set(self, e, t):
-        (e.set_robot_params if self.kind == "rp" else e.set_contact_normals)(t)
-
-    def bind(self, e, t):
-        (e.bind_device_robot_params if self.kind == "rp" else e.bind_device_contact_normals)(t)
-
-    def get(self, e):
-        return e.robot_params() if self.kind == "rp" else e.contact_normals()
+TABLES = {"rp": (T.Table("robot_params"), rp_table, (7, 8, 9)), "cn": (T.Table("contact_normals"), cn_table, (5, 6, 7))}
 
 
 @pytest.mark.parametrize("kind", ["rp", "cn"])
@@ -175,16 +105,16 @@ def test_table_precedence(kind):
     import torch
 
     B = 4
-    T = Table(kind, B)
-    own1, dev, own2 = T.tables
+    tab, make, seeds = TABLES[kind]
+    own1, dev, own2 = (make(B, seed) for seed in seeds)
     inp = workloads.rl_random(B, seed=91)
 
     def direct(t):
         e = Engine(B)
         load(e, inp)
         if t is not None:
-            T.set(e, t)
-        back = T.get(e)
+            tab.set(e, t)
+        back = tab.get(e)
         e.step(STATELESS)
         out = e.outputs()
         e.close()
@@ -202,26 +132,26 @@ def test_table_precedence(kind):
     load(e, inp)
 
     def check(name, what):
-        assert np.array_equal(T.get(e), want[name][0]), what
+        assert np.array_equal(tab.get(e), want[name][0]), what
         e.step(STATELESS)
-        assert_identical(e.outputs(), want[name][1], what)
+        assert_identical(e.outputs(), want[name][1], what=what)
 
     check("none", "at creation")
-    T.set(e, own1)
+    tab.set(e, own1)
     check("own1", "own table set")
     with pytest.raises(WbcError) as ei:
-        T.bind(e, d_odd.data_ptr() + 8)
+        tab.bind(e, d_odd.data_ptr() + 8)
     assert f"({ERR_ARG})" in str(ei.value) and "16-byte aligned" in str(ei.value)
     check("own1", "after a refused bind")
-    T.bind(e, d_dev)
+    tab.bind(e, d_dev)
     check("dev", "device table bound over the own one")
-    T.set(e, None)
+    tab.set(e, None)
     check("dev", "own table cleared under a bound one")
-    T.set(e, own2)
+    tab.set(e, own2)
     check("dev", "own table set again under a bound one")
-    T.bind(e, 0)
+    tab.bind(e, 0)
     check("own2", "unbound: the own table")
-    T.set(e, None)
+    tab.set(e, None)
     check("none", "cleared")
     e.close()
 
@@ -259,17 +189,17 @@ def test_bindings_survive_a_cycle(B, flags):
         return {k: d_out[k].cpu().numpy() for k in KEYS}
 
     e.step(STATELESS)
-    assert_identical(caller_buffers(), want["a"], "first step")
+    assert_identical(caller_buffers(), want["a"], what="first step")
     for t in d_out.values():
         t.fill_(-1)
     torch.cuda.synchronize()
     got_b = cycle(e, b, STATELESS | flags)
-    assert_identical(got_b, want["b"], "the cycle")
+    assert_identical(got_b, want["b"], what="the cycle")
     after = caller_buffers()
     for k in KEYS:  # the cycle wrote none of the caller's buffers
         assert np.all(after[k] == -1), k
     e.step(STATELESS)
-    assert_identical(caller_buffers(), want["a"], "the step after the cycle")
+    assert_identical(caller_buffers(), want["a"], what="the step after the cycle")
     assert e.device_outputs() == {k: d_out[k].data_ptr() for k in KEYS}
     e.close()
 
@@ -303,6 +233,6 @@ def test_each_instance_is_reached(step):
             outs[tables + "2"] = e.outputs()
         e.close()
     for tables in ("rp", "cn"):
-        assert_identical(outs[tables], outs["plain"], (step, tables))
+        assert_identical(outs[tables], outs["plain"], what=(step, tables))
         if step == "stateful":
-            assert_identical(outs[tables + "2"], outs["plain2"], (step, tables, "second step"))
+            assert_identical(outs[tables + "2"], outs["plain2"], what=(step, tables, "second step"))

@@ -5,7 +5,6 @@ report of the four new kernel units."""
 import itertools
 import os
 import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -15,10 +14,9 @@ import limits_oracle as LO
 import qp_ipm as Q
 import wbc_np as W
 from quadrupedwholebodycontroller_amd import _capi, limits_row, limits_table, workloads
-from test_robot_params_cpu import _report
+from unit_reports import build_host_program, report, run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
 
 
 def test_names_follow_the_header():
@@ -193,22 +191,7 @@ int main(int argc, char** argv) {
 def layout_bin(tmp_path_factory):
     """The program above, built with the address and undefined-behaviour sanitizers when the host
     toolchain links them (a stand-alone program: nothing is preloaded), else without."""
-    d = tmp_path_factory.mktemp("limits")
-    src = d / "l.cpp"
-    src.write_text(PROG)
-    exe = d / "l"
-    cmd = ["g++", "-O1", "-g", "-Wall", "-Wno-unused-result", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           str(src), "-o", str(exe)]
-    san = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True)
-    if san.returncode != 0 or subprocess.run([str(exe), "names"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    return str(exe)
-
-
-def _run(exe, mode, text=""):
-    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return [l.split() for l in r.stdout.splitlines()]
+    return build_host_program(tmp_path_factory.mktemp("limits"), "l", PROG)
 
 
 def test_lm_bad_column_host(layout_bin):
@@ -230,7 +213,7 @@ def test_lm_bad_column_host(layout_bin):
     cases += [(edit((24 + l, 0.0)), -1) for l in range(4)] + [(edit((24 + l, -1e-300)), 24 + l) for l in range(4)]
     cases += [(edit((24, -0.0)), -1), (edit((5, -1e308), (17, 1e308)), -1)]
     text = "".join(" ".join(repr(float(v)) for v in r) + "\n" for r, _ in cases)
-    got = [int(l[0]) for l in _run(layout_bin, "rows", text)]
+    got = [int(l[0]) for l in run_host_program(layout_bin, "rows", text)]
     assert len(got) == len(cases)
     for (r, want), g in zip(cases, got):
         assert g == want == _capi.limits_bad_column(r), (r, want, g)
@@ -241,10 +224,10 @@ def test_instance_choice_and_argument_check_with_lm(layout_bin):
     lm0 / lm1 whatever else is set, and without it (the default) returns what it returned; step_args_refused
     for an LM instance refuses what its bb instance refuses, and a missing limits table; the old argument
     lists return what they returned."""
-    names = {n: int(i) for i, n in _run(layout_bin, "names")}
+    names = {n: int(i) for i, n in run_host_program(layout_bin, "names")}
     assert names.pop("count") == 9 and names.pop("all") == 12 and names.pop("every") == 14
     assert [names[n] for n in ("lm0", "lm1")] == [12, 13] and sorted(names.values()) == list(range(14))
-    for lm, bb, cn, rp, all_stance, stateful, got, with_bb, plain in ([int(v) for v in r] for r in _run(layout_bin, "instance")):
+    for lm, bb, cn, rp, all_stance, stateful, got, with_bb, plain in ([int(v) for v in r] for r in run_host_program(layout_bin, "instance")):
         assert 0 <= plain < 9 and (with_bb == plain if not bb else 9 <= with_bb < 12)
         assert got == (names["lm1" if stateful else "lm0"] if lm else with_bb), (lm, bb, cn, rp, all_stance, stateful)
     insts = list(itertools.product((0, 1), repeat=6))
@@ -252,7 +235,7 @@ def test_instance_choice_and_argument_check_with_lm(layout_bin):
             for n, s, m, q, r, c, b, l in itertools.product((-1, 3), (0, 1, 2), (0, 4), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1))]
     text = "".join(" ".join(str(v) for v in (*inst, a["nwaves"], a["stateful"], a["modes"], a["qmap"], a["rp"], a["cn"], a["bb"],
                                              a["lm"])) + "\n" for inst in insts for a in args)
-    got = iter([int(v) for v in l] for l in _run(layout_bin, "refused", text))
+    got = iter([int(v) for v in l] for l in run_host_program(layout_bin, "refused", text))
     units = {(0, 0, 1, 1, 1, 1): "lm0", (1, 0, 1, 1, 1, 1): "lm1"}
     seen = {u: [0, 0] for u in units.values()}
     for inst in insts:
@@ -284,7 +267,7 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
     multipliers (that frame, 980 B against 956 B, is why the duals stage is in units of its own).  Each unit
     holds its kernel and one drain_fallbacks."""
     with ThreadPoolExecutor(2) as ex:
-        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+        (new, asm), (old, _) = ex.map(lambda a: report(*a), [(unit, var), (base, base_var)])
     assert len(new) == 1 and len(old) == 1, (list(new), list(old))
     (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
     assert kernel in name, name

@@ -6,7 +6,6 @@ wbc_set_robot_params validates on the host, but it needs an engine and an engine
 the validation's test is tests/test_gpu_robot_params.py's."""
 import os
 import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -14,9 +13,9 @@ import pytest
 
 import wbc_ref as R
 from quadrupedwholebodycontroller_amd import ROBOT_PARAM_NAMES, _capi, robot_param_table
+from unit_reports import report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
 
 
 def test_names_follow_the_header():
@@ -50,31 +49,6 @@ def test_table_forms():
             robot_param_table(B, p, bad)
 
 
-def _report(unit, var):
-    """The compiler's resource report (-Rpass-analysis=kernel-resource-usage) of a one-kernel unit
-    under its Makefile flags, {kernel: {field: value}}, and its device assembly."""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    waves = re.search(r"^WAVES \?= (\d+)", mk, re.M).group(1)
-    kflags = re.search(r"^KFLAGS := (.*)$", mk, re.M).group(1).split()
-    sflags = re.search(rf"^{var} := (.*)$", mk, re.M).group(1).split()
-    assert unit in re.search(r"^KTU := (.*)$", mk, re.M).group(1).split()
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"),
-                        "-I", CSRC, f"-DWBC_WAVES_PER_SIMD={waves}", *kflags, *sflags, "-S", "--offload-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, f"wbc_kernel_{unit}.hip"), "-o", "-"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.split("\n"):
-        m = re.search(r"remark:\s+(.*?):\s+(\S+) \[-Rpass-analysis", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            cur = out.setdefault(m.group(2), {})
-        elif cur is not None and m.group(2).isdigit():
-            cur[m.group(1)] = int(m.group(2))
-    return out, r.stdout
-
-
 @pytest.mark.parametrize("unit,var,kernel,base,base_var", [
     ("rp0", "RP0_KFLAGS", "wbc_update_solve_kernelILi0ELb0ELb1E", "step0", "STEP0_KFLAGS"),
     ("rp1", "RP1_KFLAGS", "wbc_update_solve_kernelILi1ELb0ELb1E", "step1", "STEP1_KFLAGS"),
@@ -90,7 +64,7 @@ def test_new_units_resources(unit, var, kernel, base, base_var):
     instance reports; and, as tests/test_kernel_resources.py checks the existing units, the kernel's
     own body holds no scratch instruction and the unit holds the kernel and its fallback callee only."""
     with ThreadPoolExecutor(2) as ex:
-        (new, asm), (old, _) = ex.map(lambda a: _report(*a), [(unit, var), (base, base_var)])
+        (new, asm), (old, _) = ex.map(lambda a: report(*a), [(unit, var), (base, base_var)])
     assert len(new) == 1 and len(old) == 1, (list(new), list(old))
     (name, rep), (_, ref) = next(iter(new.items())), next(iter(old.items()))
     assert kernel in name, name

@@ -108,13 +108,13 @@ def test_literal_and_reduced_agree_on_status():
 
 
 def test_literal_and_reduced_grf_under_the_table():
-    """The reference's own error on grf under test_gpu_robot_params.table(8, 11), robot b under row b,
+    """The reference's own error on grf under table_steps.table(8, 11), robot b under row b,
     in the GPU tests' measure max|a - b| / (1 + max|grf|): the two QP forms against each other (forces
     near zero beside accelerations of 1e3 keep the literal 42 x 70 solve's absolute noise), and the
     12-variable form against itself with every input moved by at most one ulp (a barely loaded stance
     leg on the edge of its friction cone).  Both are far above the spread on tau; ten times the larger
     (6.7e-11), rounded up, is margins.STATEFUL_TABLE_GRF."""
-    from test_gpu_robot_params import row_dict, table  # plain helpers: importing them needs no GPU
+    from table_steps import row_dict, table
 
     rows, g = table(B, 11), np.random.default_rng(0)
     for latch in (True, False):

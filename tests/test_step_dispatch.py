@@ -10,13 +10,10 @@ cycle blocks, compiled for the host from the engine's own header:
   packed blocks [pose | nu | qj | ref | contacts | switching] and [tau | grf | status | iters | x],
   against the sizes and offsets the engine computed by hand."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
+from unit_reports import build_host_program, run_host_program
 
 PROG = r"""
 #include <cstdio>
@@ -84,22 +81,7 @@ int main(int argc, char** argv) {
 def layout_bin(tmp_path_factory):
     """The program above, built with the address and undefined-behaviour sanitizers when the host
     toolchain links them (a stand-alone program: nothing is preloaded), else without."""
-    d = tmp_path_factory.mktemp("dispatch")
-    src = d / "d.cpp"
-    src.write_text(PROG)
-    exe = d / "d"
-    cmd = ["g++", "-O1", "-g", "-Wall", "-Wno-unused-result", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-           str(src), "-o", str(exe)]
-    san = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True)
-    if san.returncode != 0 or subprocess.run([str(exe), "names"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    return str(exe)
-
-
-def run(exe, mode, text=""):
-    r = subprocess.run([exe, mode], input=text, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return [l.split() for l in r.stdout.splitlines()]
+    return build_host_program(tmp_path_factory.mktemp("dispatch"), "d", PROG)
 
 
 # The nine launchers as they were written by hand, one per kernel unit: (STF, SONLY, RP, CN) and the
@@ -136,7 +118,7 @@ def test_argument_check_is_the_nine_hand_written_ones(layout_bin):
     assert len(insts) == 16 and len(ARGS) >= 36
     text = "".join(" ".join(str(v) for v in (*inst, a["nwaves"], a["stateful"], a["modes"], a["qmap"], a["rp"], a["cn"])) + "\n"
                    for inst in insts for a in ARGS)
-    got = iter(int(l[0]) for l in run(layout_bin, "refused", text))
+    got = iter(int(l[0]) for l in run_host_program(layout_bin, "refused", text))
     units = {inst: rule for inst, rule in HAND_WRITTEN.values()}
     assert len(units) == 9
     for inst in insts:
@@ -167,10 +149,10 @@ def earlier_chain(cn, rp, all_stance, stateful):
 
 
 def test_instance_choice_is_the_earlier_chain(layout_bin):
-    names = {n: int(i) for i, n in run(layout_bin, "names")}
+    names = {n: int(i) for i, n in run_host_program(layout_bin, "names")}
     assert names.pop("count") == 9 and sorted(names.values()) == list(range(9))
     assert sorted(names) == sorted(HAND_WRITTEN)
-    rows = run(layout_bin, "instance")
+    rows = run_host_program(layout_bin, "instance")
     assert len(rows) == 16
     for cn, rp, all_stance, stateful, got in ([int(v) for v in r] for r in rows):
         if all_stance and stateful:
@@ -183,7 +165,7 @@ def test_instance_choice_is_the_earlier_chain(layout_bin):
 
 @pytest.mark.parametrize("B", [1, 3, 4, 5, 64, 65])
 def test_block_views(layout_bin, B):
-    (row,) = run(layout_bin, "blocks", f"{B}\n")
+    (row,) = run_host_program(layout_bin, "blocks", f"{B}\n")
     v = [int(x) for x in row]
     assert v[0] == B and v[1] == 1  # the const views name the same arrays
     pose, nu, qj, ref, contacts, switching, tau, grf, status, iters, x = v[2:13]

@@ -16,90 +16,49 @@ and, with --parent-lib, `parent`: the plain step of another build of the library
 an engine of its own, in the same rotation.  Prints one JSON line per workload with the median us per
 step of each, the ratios to the plain step, and duals over bb (host-copied and device-bound masks)."""
 import argparse
-import json
-import os
-import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-WORKLOADS = (("stance_cold", 4096, 1), ("rl_random", 8192, 3))
+import step_timing_common as T
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--parent-lib", default=None)
+    T.add_timing_arguments(ap, steps=200, warmup=20, rounds=7)
     args = ap.parse_args()
     import torch
 
-    from quadrupedwholebodycontroller_amd import DUALS, STATELESS, Engine, _capi, workloads
+    from quadrupedwholebodycontroller_amd import DUALS, STATELESS, workloads
 
     stream = torch.cuda.Stream()
-
-    def engine(inp, lib_path=None):
-        if lib_path:  # an engine of another build: its own library handle, this build's Python wrapper
-            own, _capi._lib = _capi._lib, None
-            try:
-                _capi.load_library(os.path.abspath(lib_path))
-                e = Engine(len(inp["contacts"]))
-            finally:
-                _capi._lib = own
-        else:
-            e = Engine(len(inp["contacts"]))
-        e.set_stream(stream)
-        e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-        e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-        return e
-
-    def timed(e, flags):
-        for _ in range(args.warmup):
-            e.step(flags)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(stream)
-        for _ in range(args.steps):
-            e.step(flags)
-        ev1.record(stream)
-        torch.cuda.synchronize()
-        return ev0.elapsed_time(ev1) / args.steps * 1e3  # us per step
-
-    Engine(4).close()  # this build's library is the process's default before another one is loaded
-    for gen, B, seed in WORKLOADS:
+    T.first_engine()
+    for gen, B, seed in T.WORKLOADS:
         inp = getattr(workloads, gen)(B, seed=seed)
-        e = engine(inp)
-        parent = engine(inp, args.parent_lib) if args.parent_lib else None
+        e = T.engine(inp, None, stream)
+        parent = T.engine(inp, args.parent_lib, stream) if args.parent_lib else None
         default = e.base_body()
         masks = torch.from_numpy(inp["contacts"]).cuda()
         torch.cuda.synchronize()
-        forms = [("plain", None, STATELESS, False), ("bb", default, STATELESS, False), ("duals", None, STATELESS | DUALS, False),
-                 ("bb_dev", default, STATELESS, True), ("duals_dev", None, STATELESS | DUALS, True)]
-        us = {name: [] for name, *_ in forms}
-        if parent:
-            us["parent"] = []
-        for _ in range(args.rounds):
-            for name, rows, flags, dev in forms:
+
+        def form(rows, flags, dev):
+            def measure():
                 e.set_base_body(rows)
                 e.bind_device_inputs(contacts=masks.data_ptr() if dev else 0)
-                us[name].append(timed(e, flags))
-            if parent:
-                us["parent"].append(timed(parent, STATELESS))
+                return T.timed(e, args.steps, args.warmup, stream, flags)
+            return measure
+
+        forms = [("plain", form(None, STATELESS, False)), ("bb", form(default, STATELESS, False)),
+                 ("duals", form(None, STATELESS | DUALS, False)), ("bb_dev", form(default, STATELESS, True)),
+                 ("duals_dev", form(None, STATELESS | DUALS, True))]
+        if parent:
+            forms.append(("parent", lambda: T.timed(parent, args.steps, args.warmup, stream, STATELESS)))
+        us = T.rotate(args.rounds, forms)
         e.set_base_body(None)
         e.bind_device_inputs()
         e.close()
         if parent:
             parent.close()
-        med = {k: float(np.median(v)) for k, v in us.items()}
-        print(json.dumps({"workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds,
-                          "us_per_step": {k: round(v, 3) for k, v in med.items()},
-                          "us_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in us.items()},
-                          "over_plain": {k: round(v / med["plain"], 4) for k, v in med.items()},
-                          "duals_over_bb": round(med["duals"] / med["bb"], 4),
-                          "duals_dev_over_bb_dev": round(med["duals_dev"] / med["bb_dev"], 4),
-                          "plain_over_parent": round(med["plain"] / med["parent"], 4) if parent else None}), flush=True)
+        T.report({"workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds}, us,
+                 lambda m: {"duals_over_bb": T.ratio(m, "duals", "bb"), "duals_dev_over_bb_dev": T.ratio(m, "duals_dev", "bb_dev"),
+                            "plain_over_parent": T.ratio(m, "plain", "parent")})
 
 
 if __name__ == "__main__":

@@ -17,42 +17,24 @@ library (the parent commit's) on an engine of its own, in the same rotation.  Th
 times; one JSON line per workload and pass with the median us per step of each form, fn over lm (the table's own
 cost), seed7 over fn, and this build's plain and lm steps over the parent's."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-WORKLOADS = (("stance_cold", 4096, 1), ("rl_random", 8192, 3))
+import step_timing_common as T
 
 
 def oracle_passes(n):
     """Mean active-set passes of the numpy oracle on n robots per workload, no bounds against table(n, 7)."""
     import force_bounds_oracle as FO
-    from quadrupedwholebodycontroller_amd import workloads
 
-    for gen, _, seed in WORKLOADS:
-        inp = getattr(workloads, gen)(n, seed=seed)
-        res = {}
-        for name, t in (("default", np.tile(FO.NONE, (n, 1))), ("seed7", FO.table(n))):
-            r = FO.run_batch(inp, t)
-            res[name] = dict(ok=int((r["status"] == 0).sum()), mean_passes=round(float(r["iters"].mean()), 3),
-                             max_passes=int(r["iters"].max()), tight=FO.tight_robots(r["grf"], r["status"], inp["contacts"], t))
-        print(json.dumps({"workload": gen, "robots": n, **res}), flush=True)
+    T.oracle_passes(n, lambda n: (("default", np.tile(FO.NONE, (n, 1))), ("seed7", FO.table(n))), FO.run_batch,
+                    lambda r, t, inp: FO.tight_robots(r["grf"], r["status"], inp["contacts"], t))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--rounds", type=int, default=5)
+    T.add_timing_arguments(ap, steps=2000, warmup=50, rounds=5)
     ap.add_argument("--passes", type=int, default=2)
-    ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--oracle-passes", type=int, default=0)
     args = ap.parse_args()
     if args.oracle_passes:
@@ -60,73 +42,45 @@ def main():
     import torch
 
     import force_bounds_oracle as FO
-    from quadrupedwholebodycontroller_amd import STATELESS, Engine, _capi, workloads
+    from quadrupedwholebodycontroller_amd import STATELESS, workloads
 
     stream = torch.cuda.Stream()
-
-    def engine(inp, lib_path=None):
-        if lib_path:  # an engine of another build: its own library handle, this build's Python wrapper
-            own, _capi._lib = _capi._lib, None
-            try:
-                _capi.load_library(os.path.abspath(lib_path))
-                e = Engine(len(inp["contacts"]))
-            finally:
-                _capi._lib = own
-        else:
-            e = Engine(len(inp["contacts"]))
-        e.set_stream(stream)
-        e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-        e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-        return e
-
-    def timed(e):
-        for _ in range(args.warmup):
-            e.step(STATELESS)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(stream)
-        for _ in range(args.steps):
-            e.step(STATELESS)
-        ev1.record(stream)
-        torch.cuda.synchronize()
-        return ev0.elapsed_time(ev1) / args.steps * 1e3  # us per step
-
-    Engine(4).close()  # this build's library is the process's default before another one is loaded
+    T.first_engine()
     for p in range(args.passes):
-        for gen, B, seed in WORKLOADS:
+        for gen, B, seed in T.WORKLOADS:
             inp = getattr(workloads, gen)(B, seed=seed)
-            e = engine(inp)
-            parent = engine(inp, args.parent_lib) if args.parent_lib else None
+            e = T.engine(inp, None, stream)
+            parent = T.engine(inp, args.parent_lib, stream) if args.parent_lib else None
             uniform, none, seed7 = e.limits(), e.force_bounds(), FO.table(B)
-            forms = [("plain", None, None), ("lm", uniform, None), ("fn", uniform, none), ("fn_only", None, none),
-                     ("seed7", uniform, seed7)]
-            us = {name: [] for name, *_ in forms}
-            if parent:
-                us["parent"], us["parent_lm"] = [], []
-            for _ in range(args.rounds):
-                for name, lm, fn in forms:
+
+            def form(lm, fn):
+                def measure():
                     e.set_limits(lm)
                     e.set_force_bounds(fn)
-                    us[name].append(timed(e))
-                if parent:
-                    parent.set_limits(None)
-                    us["parent"].append(timed(parent))
-                    parent.set_limits(uniform)
-                    us["parent_lm"].append(timed(parent))
+                    return T.timed(e, args.steps, args.warmup, stream, STATELESS)
+                return measure
+
+            def parent_form(lm):
+                def measure():
+                    parent.set_limits(lm)
+                    return T.timed(parent, args.steps, args.warmup, stream, STATELESS)
+                return measure
+
+            forms = [("plain", form(None, None)), ("lm", form(uniform, None)), ("fn", form(uniform, none)),
+                     ("fn_only", form(None, none)), ("seed7", form(uniform, seed7))]
+            if parent:
+                forms += [("parent", parent_form(None)), ("parent_lm", parent_form(uniform))]
+            us = T.rotate(args.rounds, forms)
             e.set_limits(None)
             e.set_force_bounds(None)
             e.close()
             if parent:
                 parent.set_limits(None)
                 parent.close()
-            med = {k: float(np.median(v)) for k, v in us.items()}
-            print(json.dumps({"pass": p, "workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds,
-                              "us_per_step": {k: round(v, 3) for k, v in med.items()},
-                              "us_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in us.items()},
-                              "fn_over_lm": round(med["fn"] / med["lm"], 4),
-                              "fn_only_over_lm": round(med["fn_only"] / med["lm"], 4),
-                              "seed7_over_fn": round(med["seed7"] / med["fn"], 4),
-                              "plain_over_parent_plain": round(med["plain"] / med["parent"], 4) if parent else None,
-                              "lm_over_parent_lm": round(med["lm"] / med["parent_lm"], 4) if parent else None}), flush=True)
+            T.report({"pass": p, "workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds}, us,
+                     lambda m: {"fn_over_lm": T.ratio(m, "fn", "lm"), "fn_only_over_lm": T.ratio(m, "fn_only", "lm"),
+                                "seed7_over_fn": T.ratio(m, "seed7", "fn"), "plain_over_parent_plain": T.ratio(m, "plain", "parent"),
+                                "lm_over_parent_lm": T.ratio(m, "lm", "parent_lm")}, over_plain=False)
 
 
 if __name__ == "__main__":

@@ -17,41 +17,23 @@ and, with --parent-lib, `parent`: the plain step of another build of the library
 engine of its own, in the same rotation.  Prints one JSON line per workload with the median us per step of
 each, the ratios to the plain step, and lm over bb: the table's own cost."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-WORKLOADS = (("stance_cold", 4096, 1), ("rl_random", 8192, 3))
+import step_timing_common as T
 
 
 def oracle_passes(n):
     """Mean active-set passes of the numpy oracle on n robots per workload, default rows against table(n, 7)."""
     import limits_oracle as LO
-    from quadrupedwholebodycontroller_amd import workloads
 
-    for gen, _, seed in WORKLOADS:
-        inp = getattr(workloads, gen)(n, seed=seed)
-        res = {}
-        for name, t in (("default", np.tile(LO.default_row(), (n, 1))), ("seed7", LO.table(n))):
-            r = LO.run_batch(inp, t)
-            res[name] = dict(ok=int((r["status"] == 0).sum()), mean_passes=round(float(r["iters"].mean()), 3),
-                             max_passes=int(r["iters"].max()), tight=LO.tight_torque_robots(r, t))
-        print(json.dumps({"workload": gen, "robots": n, **res}), flush=True)
+    T.oracle_passes(n, lambda n: (("default", np.tile(LO.default_row(), (n, 1))), ("seed7", LO.table(n))), LO.run_batch,
+                    lambda r, t, inp: LO.tight_torque_robots(r, t))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--parent-lib", default=None)
+    T.add_timing_arguments(ap, steps=2000, warmup=50, rounds=5)
     ap.add_argument("--oracle-passes", type=int, default=0)
     args = ap.parse_args()
     if args.oracle_passes:
@@ -59,72 +41,40 @@ def main():
     import torch
 
     import limits_oracle as LO
-    from quadrupedwholebodycontroller_amd import STATELESS, Engine, _capi, workloads
+    from quadrupedwholebodycontroller_amd import STATELESS, workloads
 
     stream = torch.cuda.Stream()
-
-    def engine(inp, lib_path=None):
-        if lib_path:  # an engine of another build: its own library handle, this build's Python wrapper
-            own, _capi._lib = _capi._lib, None
-            try:
-                _capi.load_library(os.path.abspath(lib_path))
-                e = Engine(len(inp["contacts"]))
-            finally:
-                _capi._lib = own
-        else:
-            e = Engine(len(inp["contacts"]))
-        e.set_stream(stream)
-        e.set_state(inp["base_pose"], inp["nu"], inp["qj"])
-        e.set_reference(inp["ref"], inp["contacts"], inp["switching"])
-        return e
-
-    def timed(e):
-        for _ in range(args.warmup):
-            e.step(STATELESS)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(stream)
-        for _ in range(args.steps):
-            e.step(STATELESS)
-        ev1.record(stream)
-        torch.cuda.synchronize()
-        return ev0.elapsed_time(ev1) / args.steps * 1e3  # us per step
-
-    Engine(4).close()  # this build's library is the process's default before another one is loaded
-    for gen, B, seed in WORKLOADS:
+    T.first_engine()
+    for gen, B, seed in T.WORKLOADS:
         inp = getattr(workloads, gen)(B, seed=seed)
-        e = engine(inp)
-        parent = engine(inp, args.parent_lib) if args.parent_lib else None
+        e = T.engine(inp, None, stream)
+        parent = T.engine(inp, args.parent_lib, stream) if args.parent_lib else None
         base, uniform, seed7 = e.base_body(), e.limits(), LO.table(B)
         masks = torch.from_numpy(inp["contacts"]).cuda()
         torch.cuda.synchronize()
-        forms = [("plain", None, None, False), ("bb", base, None, False), ("bb_dev", base, None, True),
-                 ("lm", None, uniform, False), ("seed7", None, seed7, False)]
-        us = {name: [] for name, *_ in forms}
-        if parent:
-            us["parent"] = []
-        for _ in range(args.rounds):
-            for name, rows, lm, dev in forms:
+
+        def form(rows, lm, dev):
+            def measure():
                 e.set_base_body(rows)
                 e.set_limits(lm)
                 e.bind_device_inputs(contacts=masks.data_ptr() if dev else 0)
-                us[name].append(timed(e))
-            if parent:
-                us["parent"].append(timed(parent))
+                return T.timed(e, args.steps, args.warmup, stream, STATELESS)
+            return measure
+
+        forms = [("plain", form(None, None, False)), ("bb", form(base, None, False)), ("bb_dev", form(base, None, True)),
+                 ("lm", form(None, uniform, False)), ("seed7", form(None, seed7, False))]
+        if parent:
+            forms.append(("parent", lambda: T.timed(parent, args.steps, args.warmup, stream, STATELESS)))
+        us = T.rotate(args.rounds, forms)
         e.set_base_body(None)
         e.set_limits(None)
         e.bind_device_inputs()
         e.close()
         if parent:
             parent.close()
-        med = {k: float(np.median(v)) for k, v in us.items()}
-        print(json.dumps({"workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds,
-                          "us_per_step": {k: round(v, 3) for k, v in med.items()},
-                          "us_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in us.items()},
-                          "over_plain": {k: round(v / med["plain"], 4) for k, v in med.items()},
-                          "lm_over_bb": round(med["lm"] / med["bb"], 4),
-                          "lm_over_bb_dev": round(med["lm"] / med["bb_dev"], 4),
-                          "seed7_over_lm": round(med["seed7"] / med["lm"], 4),
-                          "plain_over_parent_plain": round(med["plain"] / med["parent"], 4) if parent else None}), flush=True)
+        T.report({"workload": gen, "batch": B, "steps": args.steps, "rounds": args.rounds}, us,
+                 lambda m: {"lm_over_bb": T.ratio(m, "lm", "bb"), "lm_over_bb_dev": T.ratio(m, "lm", "bb_dev"),
+                            "seed7_over_lm": T.ratio(m, "seed7", "lm"), "plain_over_parent_plain": T.ratio(m, "plain", "parent")})
 
 
 if __name__ == "__main__":
