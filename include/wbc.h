@@ -132,6 +132,9 @@ enum {
                           * state's best feasible hypothesis (wbc_get_best_modes / wbc_device_best_modes) */
 #define WBC_DUALS 2048u  /* wbc_step only (default form): also write each robot's QP multipliers of the friction
                           * faces and torque limits (wbc_get_duals / wbc_device_duals) */
+#define WBC_DUALS_FORCE 4096u /* wbc_step only (default form), implies WBC_DUALS: the same 40 multipliers and the 8 of
+                          * the per-foot normal-force bounds, 48 per robot (wbc_get_force_duals /
+                          * wbc_device_force_duals); allowed with and without a force-bound table in force */
 
 /* Debug record layout (doubles per robot), written by update/step under WBC_DEBUG. */
 enum {
@@ -266,6 +269,33 @@ int32_t wbc_synchronize(wbc_engine* h);
 enum { WBC_DUAL_LEN = 40 };
 int32_t wbc_get_duals(wbc_engine* h, double* dual /* [B][40] */);
 int32_t wbc_device_duals(wbc_engine* h, double** d_dual);
+/* The same under per-foot normal-force bounds (wbc_set_force_bounds below): wbc_step(flags | WBC_DUALS_FORCE)
+ * in its default form writes dual[b * WBC_DUAL_FORCE_LEN + r] for robot b.  Entries 0..39 are WBC_DUALS' own,
+ * in the same numbering, and
+ *     r = 40 + 2 leg + side         the leg's force row: side 0 is n_l . f_l >= fn_min[l],
+ *                                   side 1 is n_l . f_l <= fn_max[l]
+ * holds the multiplier lambda_r >= 0 of that row in newtons of normal force: what one newton more of
+ * fn_max (or less of fn_min) would buy, so a foot held by its load ramp and not by its friction cone shows
+ * a non-zero entry 41 + 2 leg and zero faces.  In qpOASES' sign convention for the two-sided row,
+ * y = lambda_side0 - lambda_side1.  An entry is 0 for a row that does not exist (an infinite bound, a foot
+ * in swing) or does not bind, and all 48 are 0 unless the status is WBC_QP_OK.  A force row contains no
+ * slack and none of the eliminated variables' own rows, so the elimination argument above covers it
+ * (DESIGN.md 23).
+ * The flag implies WBC_DUALS (that bit is ignored beside it); WBC_DUALS alone stays what it is, 40 entries,
+ * and stays refused while a force-bound table is in force.  Allowed as WBC_DUALS is (stateless, stateful,
+ * WBC_COLD, WBC_DEBUG, WBC_NO_X, WBC_TIMED, WBC_GROUP, any combination of the per-robot tables), with or
+ * without a force-bound table: without one the step runs under the engine's own no-bounds table, entries
+ * 40..47 are 0 and entries 0..39 hold WBC_DUALS' bits, so a caller who switches a load ramp on and off
+ * keeps one code path.  tau, grf, x, status and iters are bit-identical to the step without the flag.
+ * The buffer is the engine's own ([B][48], apart from WBC_DUALS' [B][40]: the strides differ, so neither
+ * stands in for the other), allocated at the first step that carries the flag, written on the engine's
+ * stream and freed by wbc_destroy.  wbc_get_force_duals is synchronous.  Both getters return WBC_ERR_STATE
+ * unless the last wbc_step carried WBC_DUALS_FORCE, and after such a step wbc_get_duals / wbc_device_duals
+ * return WBC_ERR_STATE.  WBC_DUALS_FORCE with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, or on wbc_update /
+ * wbc_solve / wbc_cycle / wbc_step_modes, is WBC_ERR_ARG. */
+enum { WBC_DUAL_FORCE_LEN = 48 };
+int32_t wbc_get_force_duals(wbc_engine* h, double* dual /* [B][48] */);
+int32_t wbc_device_force_duals(wbc_engine* h, double** d_dual);
 
 /* Contact-mode hypotheses (BASELINE configs[4]: every state solved under several contact masks).
  * After wbc_set_modes(h, K, modes) with K dividing the batch B, the engine holds S = B / K states:
@@ -500,7 +530,8 @@ enum {
  * and the plain wbc_cycle, with any of the other per-robot tables in force.  Refused with
  * WBC_ERR_STATE: wbc_update, wbc_solve, wbc_step_modes, wbc_step / wbc_cycle with WBC_SPLIT, WBC_FUSED
  * or WBC_RESIDENT, and wbc_step with WBC_DUALS (a binding force row has no entry among the 40
- * multipliers). */
+ * multipliers).  WBC_DUALS_FORCE gives the multipliers under the table: the 40 and the force rows' 8
+ * (wbc_get_force_duals above). */
 int32_t wbc_set_force_bounds(wbc_engine* h, const double* table);
 /* Caller-owned device table [B][WBC_FN_LEN] (no copy, no host validation; 16-byte aligned; a caller may
  * rewrite it on the engine's stream every cycle).  NULL restores the engine-owned table, or none.  On

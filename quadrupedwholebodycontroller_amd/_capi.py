@@ -21,6 +21,9 @@ OBJECTIVE, BEST = 512, 1024
 # wbc_step only (default form): each robot's QP multipliers of the friction faces and torque limits
 DUALS = 2048
 DUAL_LEN = 40  # WBC_DUAL_LEN: rows 4 leg + face, then 16 + 2 joint + side (side 0: tau >= -max, side 1: tau <= +max)
+# wbc_step only (default form), implies DUALS: the 40 and the multipliers of the per-foot normal-force bounds
+DUALS_FORCE = 4096
+DUAL_FORCE_LEN = 48  # WBC_DUAL_FORCE_LEN: the 40 rows, then 40 + 2 leg + side (side 0: n.f >= fn_min, side 1: n.f <= fn_max)
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
 # columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
 ROBOT_PARAM_NAMES = ("friction", "max_torque", "kp", "kp_z", "kd", "ki", "kp_swing", "kd_swing", "slack_weight")
@@ -53,6 +56,8 @@ TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bi
 MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
 # the multipliers of wbc_step (WBC_DUALS)
 DUAL_SYMBOLS = ["wbc_get_duals", "wbc_device_duals"]
+# and with the force rows' (WBC_DUALS_FORCE)
+FORCE_DUAL_SYMBOLS = ["wbc_get_force_duals", "wbc_device_force_duals"]
 
 # WBC_DBG_* offsets (include/wbc.h)
 DBG = dict(COM=0, COMVEL=3, POSE=6, VC=12, M=18, CNU=342, JFEET=360, PFEET=576, VFEET=588, MBARB=600, MBARJ=636,
@@ -64,6 +69,7 @@ C_API_SYMBOLS = [
     "wbc_set_state", "wbc_set_reference", "wbc_bind_device_inputs", "wbc_bind_device_outputs", "wbc_reset", "wbc_update", "wbc_solve",
     "wbc_step", "wbc_set_modes", "wbc_step_modes", "wbc_modes_per_wave", "wbc_cycle", "wbc_synchronize", "wbc_get_output", "wbc_device_outputs", "wbc_get_debug", "wbc_last_kernel_ms",
     "wbc_last_error", "wbc_model_from_urdf", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS, *DUAL_SYMBOLS,
+    *FORCE_DUAL_SYMBOLS,
 ]
 
 
@@ -139,9 +145,11 @@ def load_library(path: str = LIB_PATH):
         "wbc_device_best_modes": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)], I32),
         "wbc_get_duals": ([P, P], I32),
         "wbc_device_duals": ([P, C.POINTER(P)], I32),
+        "wbc_get_force_duals": ([P, P], I32),
+        "wbc_device_force_duals": ([P, C.POINTER(P)], I32),
     }
     for name, (argt, rest) in sig.items():
-        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS, *DUAL_SYMBOLS) and not hasattr(lib, name):
+        if name in ("wbc_modes_per_wave", *TABLE_SYMBOLS, *MODE_OUT_SYMBOLS, *DUAL_SYMBOLS, *FORCE_DUAL_SYMBOLS) and not hasattr(lib, name):
             continue  # earlier builds loaded through WBC_LIB (A/B variants, tools/build_rev.sh) lack these
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -709,6 +717,20 @@ class Engine:
         self._check(self.lib.wbc_device_duals(self.h, C.byref(p)), "wbc_device_duals")
         return p.value
 
+    def force_duals(self) -> np.ndarray:
+        """wbc_get_force_duals: (B, 48) multipliers after step(... | DUALS_FORCE): the 40 of duals(), then the
+        per-foot normal-force bounds' (rows 40 + 2 leg + side: side 0 n.f >= fn_min, side 1 n.f <= fn_max); 0 for
+        a row that does not exist or does not bind, all 0 where status is not QP_OK.  dual_rows() reshapes them."""
+        d = np.zeros((self.batch, DUAL_FORCE_LEN))
+        self._check(self.lib.wbc_get_force_duals(self.h, _ptr(d)), "wbc_get_force_duals")
+        return d
+
+    def device_force_duals(self) -> int:
+        """wbc_device_force_duals: the device address of the (B, 48) multipliers."""
+        p = C.c_void_p()
+        self._check(self.lib.wbc_device_force_duals(self.h, C.byref(p)), "wbc_device_force_duals")
+        return p.value
+
     def objective(self) -> np.ndarray:
         """wbc_get_objective: (B,) QP objective of each hypothesis after step_modes(... | OBJECTIVE), row
         s * K + k as the other outputs; +inf where status is not QP_OK."""
@@ -745,12 +767,18 @@ class Engine:
 def dual_rows(d):
     """The (B, 40) multipliers of Engine.duals() by constraint: {"friction": (B, 4, 4) >= 0, leg by face in
     the reference's order; "torque": (B, 12) signed, side 0 - side 1: positive where joint j sits at
-    -max_torque, negative at +max_torque (qpOASES' sign of the two-sided row's multiplier)}."""
+    -max_torque, negative at +max_torque (qpOASES' sign of the two-sided row's multiplier)}.  The (B, 48)
+    multipliers of Engine.force_duals() give a third item, "force": (B, 4) signed, side 0 - side 1: positive
+    where foot l sits at fn_min, negative at fn_max."""
     d = np.asarray(d, dtype=np.float64)
-    if d.ndim != 2 or d.shape[1] != DUAL_LEN:
-        raise ValueError(f"duals: need shape (B, {DUAL_LEN}), got {d.shape}")
-    t = d[:, 16:].reshape(-1, NUM_JOINTS, 2)
-    return {"friction": d[:, :16].reshape(-1, 4, 4).copy(), "torque": t[:, :, 0] - t[:, :, 1]}
+    if d.ndim != 2 or d.shape[1] not in (DUAL_LEN, DUAL_FORCE_LEN):
+        raise ValueError(f"duals: need shape (B, {DUAL_LEN}) or (B, {DUAL_FORCE_LEN}), got {d.shape}")
+    t = d[:, 16:DUAL_LEN].reshape(-1, NUM_JOINTS, 2)
+    rows = {"friction": d[:, :16].reshape(-1, 4, 4).copy(), "torque": t[:, :, 0] - t[:, :, 1]}
+    if d.shape[1] == DUAL_FORCE_LEN:
+        f = d[:, DUAL_LEN:].reshape(-1, 4, 2)
+        rows["force"] = f[:, :, 0] - f[:, :, 1]
+    return rows
 
 
 def split_debug(rec):

@@ -52,6 +52,10 @@ extern "C" hipError_t wbc_launch_update_solve_du1(const wbc::KernelArgs* a, hipS
 // and the limits units' duals instances (wbc_kernel_lmd0.hip, wbc_kernel_lmd1.hip: WBC_DUALS under a limits table)
 extern "C" hipError_t wbc_launch_update_solve_lmd0(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update_solve_lmd1(const wbc::KernelArgs* a, hipStream_t st);
+// and the force-bound units' duals instances (wbc_kernel_fnd0.hip, wbc_kernel_fnd1.hip: wbc_step with WBC_DUALS_FORCE,
+// KernelArgs::dual as [B][WBC_DUAL_FORCE_LEN])
+extern "C" hipError_t wbc_launch_update_solve_fnd0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_fnd1(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
 extern "C" hipError_t wbc_preload_resident();
@@ -147,9 +151,16 @@ struct wbc_engine {
     // the flag; step_duals: the last wbc_step carried it.  Its kernels are base-body instances, so without
     // a base-body table in force their step reads d_bb_def: base_row in B rows (built at the first use),
     // and d_cn_flat / d_rp_uni as the base-body kernels do
+    // wbc_step with WBC_DUALS_FORCE: the multipliers [B][WBC_DUAL_FORCE_LEN] in a buffer of their own (the strides
+    // differ), allocated at the first step that carries that flag; without a force-bound table in force its step
+    // reads d_fn_none: (-inf x 4, +inf x 4) in B rows (built at the first use).  step_duals: what the last wbc_step
+    // wrote, which the four getters consult
     double* d_dual = nullptr;
     double* d_bb_def = nullptr;
-    bool step_duals = false;
+    double* d_dual48 = nullptr;
+    double* d_fn_none = nullptr;
+    enum StepDuals { DUALS_NONE, DUALS_40, DUALS_48 };
+    StepDuals step_duals = DUALS_NONE;
     // per-robot torque bounds and per-foot friction (KernelArgs::lm, [B][WBC_LM_LEN]; without: -+max_torque
     // and friction).  The kernels that read them are base-body instances, so without a base-body table in
     // force their step reads d_bb_def, and d_cn_flat / d_rp_uni as the base-body kernels do
@@ -479,6 +490,11 @@ int32_t refuse_duals_flag(const char* call, uint32_t flags) {
     if (!(flags & WBC_DUALS)) return WBC_OK;
     return fail(WBC_ERR_ARG, std::string(call) + ": WBC_DUALS is a flag of the default wbc_step");
 }
+// and so does WBC_DUALS_FORCE (after every other check of the call)
+int32_t refuse_force_duals_flag(const char* call, uint32_t flags) {
+    if (!(flags & WBC_DUALS_FORCE)) return WBC_OK;
+    return fail(WBC_ERR_ARG, std::string(call) + ": WBC_DUALS_FORCE is a flag of the default wbc_step");
+}
 }  // namespace
 
 extern "C" {
@@ -620,7 +636,8 @@ int32_t wbc_destroy(wbc_engine* h) {
     if (h->res_stream) (void)hipStreamDestroy(h->res_stream);
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
-                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own, h->fn.own};
+                    h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own, h->fn.own,
+                    h->d_dual48, h->d_fn_none};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -741,6 +758,12 @@ static int32_t ensure_rp_cn_uniform(wbc_engine* h) {
 static int32_t ensure_rp_cn_bb_uniform(wbc_engine* h) {
     if (const int32_t rc = ensure_rp_cn_uniform(h)) return rc;
     return ensure_uniform(h, &h->d_bb_def, h->base_row, WBC_BB_LEN, "d_bb_def");
+}
+// and the no-bounds rows a WBC_DUALS_FORCE step reads when no force-bound table is in force
+static int32_t ensure_fn_none(wbc_engine* h) {
+    const double inf = std::numeric_limits<double>::infinity();
+    const double row[WBC_FN_LEN] = {-inf, -inf, -inf, -inf, inf, inf, inf, inf};
+    return ensure_uniform(h, &h->d_fn_none, row, WBC_FN_LEN, "d_fn_none");
 }
 
 // The three calls of a per-robot table (RobotTable), for the parameters and for the normals.  What
@@ -955,6 +978,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_tables(h, "wbc_update", flags, 0, "default wbc_step only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_update", flags)) return rc;
     if (const int32_t rc = refuse_duals_flag("wbc_update", flags)) return rc;
+    if (const int32_t rc = refuse_force_duals_flag("wbc_update", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -971,6 +995,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_mode_out_flags("wbc_solve", flags)) return rc;
     if (const int32_t rc = refuse_duals_flag("wbc_solve", flags)) return rc;
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
+    if (const int32_t rc = refuse_force_duals_flag("wbc_solve", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     WBC_HIP(launch_solves(h, a));
@@ -984,25 +1009,35 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     if (h->n_modes) return fail(WBC_ERR_STATE, "wbc_step: mode hypotheses are set (use wbc_step_modes, or wbc_set_modes(h, 0, NULL))");
     if (const int32_t rc = refuse_tables(h, "wbc_step", flags, WBC_SPLIT | WBC_FUSED, "default form only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_step", flags)) return rc;
-    const bool duals = (flags & WBC_DUALS) != 0;
+    // WBC_DUALS_FORCE implies WBC_DUALS, whose bit is ignored beside it (as WBC_BEST implies WBC_OBJECTIVE): the 48-entry
+    // form has kernels, a buffer and getters of its own, and WBC_DUALS alone keeps its refusal under force bounds
+    const bool dforce = (flags & WBC_DUALS_FORCE) != 0;
+    const bool duals = (flags & WBC_DUALS) != 0 && !dforce;
     if (duals && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
     if (duals && h->fn.in_force)
         return fail(WBC_ERR_STATE, "wbc_step: WBC_DUALS with per-foot force bounds in force (the 40 multipliers have no entry "
                                    "for a force row; clear them with wbc_set_force_bounds(h, NULL))");
-    h->step_duals = false;
-    if (duals) {  // the engine's own tables for the ones the caller has not set, and the buffer
+    if (dforce && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
+        return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS_FORCE belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
+    h->step_duals = wbc_engine::DUALS_NONE;
+    if (duals || dforce) {  // the engine's own tables for the ones the caller has not set, and the buffer
         if (const int32_t rc = ensure_rp_cn_bb_uniform(h)) return rc;
+    }
+    if (dforce && !h->fn.in_force) {
+        if (const int32_t rc = ensure_fn_none(h)) return rc;
     }
     WBC_HIP(hipSetDevice(h->device));
     if (duals && !h->d_dual) WBC_HIP(dalloc(&h->d_dual, (size_t)h->batch * WBC_DUAL_LEN));
+    if (dforce && !h->d_dual48) WBC_HIP(dalloc(&h->d_dual48, (size_t)h->batch * WBC_DUAL_FORCE_LEN));
     wbc::KernelArgs a = make_args(h, flags, io.in, io.out);
-    if (duals) {
+    if (duals || dforce) {
         if (!a.rp) a.rp = h->d_rp_uni;
         if (!a.cn) a.cn = h->d_cn_flat;
         if (!a.bb) a.bb = h->d_bb_def;
-        a.dual = h->d_dual;
+        a.dual = dforce ? h->d_dual48 : h->d_dual;
     }
+    if (dforce && !a.fn) a.fn = h->d_fn_none;  // (a missing limits table stays a null KernelArgs::lm, as in fn0 / fn1)
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
     if (timed) WBC_HIP(hipEventRecord(h->ev0, h->stream));
     if (flags & WBC_SPLIT) {
@@ -1024,7 +1059,10 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         WBC_HIP(begin_step16(h, a, flags, io.qmap));
         // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks; under
         // a limits table the limits units' own
-        if (duals && a.lm) {
+        // WBC_DUALS_FORCE: the force-bound units' duals instance, whatever the tables
+        if (dforce) {
+            WBC_HIP((a.stateful ? wbc_launch_update_solve_fnd1 : wbc_launch_update_solve_fnd0)(&a, h->stream));
+        } else if (duals && a.lm) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_lmd1 : wbc_launch_update_solve_lmd0)(&a, h->stream));
         } else if (duals) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_du1 : wbc_launch_update_solve_du0)(&a, h->stream));
@@ -1038,7 +1076,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         h->timed = true;
     }
     h->updated = false;
-    h->step_duals = duals;
+    h->step_duals = dforce ? wbc_engine::DUALS_48 : duals ? wbc_engine::DUALS_40 : wbc_engine::DUALS_NONE;
     return WBC_OK;
 }
 
@@ -1079,6 +1117,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (!(flags & WBC_STATELESS)) return fail(WBC_ERR_ARG, "wbc_step_modes: hypotheses are cold steps (WBC_STATELESS)");
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
     if (const int32_t rc = refuse_duals_flag("wbc_step_modes", flags)) return rc;
+    if (const int32_t rc = refuse_force_duals_flag("wbc_step_modes", flags)) return rc;
     const uint32_t mode_out = (flags & WBC_BEST) ? kModeOutFlags : (flags & WBC_OBJECTIVE);  // WBC_BEST implies WBC_OBJECTIVE
     if (mode_out && (flags & WBC_SPLIT))
         return fail(WBC_ERR_ARG, "wbc_step_modes: WBC_OBJECTIVE / WBC_BEST belong to the default form (not WBC_SPLIT)");
@@ -1242,6 +1281,7 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (const int32_t rc = refuse_tables(h, "wbc_cycle", flags, WBC_SPLIT | WBC_FUSED | WBC_RESIDENT, "plain cycle only")) return rc;
     if (const int32_t rc = refuse_mode_out_flags("wbc_cycle", flags)) return rc;
     if (const int32_t rc = refuse_duals_flag("wbc_cycle", flags)) return rc;
+    if (const int32_t rc = refuse_force_duals_flag("wbc_cycle", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     if (!h->h_in) {
@@ -1338,7 +1378,10 @@ int32_t wbc_get_debug(wbc_engine* h, double* out) {
 
 int32_t wbc_get_duals(wbc_engine* h, double* dual) {
     if (!h || !dual) return fail(WBC_ERR_ARG, "null argument");
-    if (!h->step_duals) return fail(WBC_ERR_STATE, "wbc_get_duals: the last wbc_step did not carry WBC_DUALS");
+    if (h->step_duals == wbc_engine::DUALS_48)
+        return fail(WBC_ERR_STATE, "wbc_get_duals: the last wbc_step carried WBC_DUALS_FORCE (48 entries per robot: "
+                                   "wbc_get_force_duals / wbc_device_force_duals)");
+    if (h->step_duals != wbc_engine::DUALS_40) return fail(WBC_ERR_STATE, "wbc_get_duals: the last wbc_step did not carry WBC_DUALS");
     WBC_HIP(hipSetDevice(h->device));
     WBC_HIP(hipMemcpyAsync(dual, h->d_dual, (size_t)h->batch * WBC_DUAL_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     WBC_HIP(hipStreamSynchronize(h->stream));
@@ -1347,8 +1390,29 @@ int32_t wbc_get_duals(wbc_engine* h, double* dual) {
 
 int32_t wbc_device_duals(wbc_engine* h, double** d_dual) {
     if (!h || !d_dual) return fail(WBC_ERR_ARG, "null argument");
-    if (!h->step_duals) return fail(WBC_ERR_STATE, "wbc_device_duals: the last wbc_step did not carry WBC_DUALS");
+    if (h->step_duals == wbc_engine::DUALS_48)
+        return fail(WBC_ERR_STATE, "wbc_device_duals: the last wbc_step carried WBC_DUALS_FORCE (48 entries per robot: "
+                                   "wbc_get_force_duals / wbc_device_force_duals)");
+    if (h->step_duals != wbc_engine::DUALS_40) return fail(WBC_ERR_STATE, "wbc_device_duals: the last wbc_step did not carry WBC_DUALS");
     *d_dual = h->d_dual;
+    return WBC_OK;
+}
+
+int32_t wbc_get_force_duals(wbc_engine* h, double* dual) {
+    if (!h || !dual) return fail(WBC_ERR_ARG, "null argument");
+    if (h->step_duals != wbc_engine::DUALS_48)
+        return fail(WBC_ERR_STATE, "wbc_get_force_duals: the last wbc_step did not carry WBC_DUALS_FORCE");
+    WBC_HIP(hipSetDevice(h->device));
+    WBC_HIP(hipMemcpyAsync(dual, h->d_dual48, (size_t)h->batch * WBC_DUAL_FORCE_LEN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    WBC_HIP(hipStreamSynchronize(h->stream));
+    return WBC_OK;
+}
+
+int32_t wbc_device_force_duals(wbc_engine* h, double** d_dual) {
+    if (!h || !d_dual) return fail(WBC_ERR_ARG, "null argument");
+    if (h->step_duals != wbc_engine::DUALS_48)
+        return fail(WBC_ERR_STATE, "wbc_device_force_duals: the last wbc_step did not carry WBC_DUALS_FORCE");
+    *d_dual = h->d_dual48;
     return WBC_OK;
 }
 

@@ -9,7 +9,8 @@
 // (WBC_STEP_DUALS), whose solves also write the QP multipliers of the friction and torque rows (20).
 // Four more hold the instances under per-robot torque bounds and per-foot friction, a sixth template
 // argument LM (21): lm0 and lm1, and lmd0 and lmd1, the same with WBC_STEP_DUALS.
-// Two more hold the instances under per-foot normal-force bounds, a seventh template argument FN (22): fn0 and fn1.
+// Two more hold the instances under per-foot normal-force bounds, a seventh template argument FN (22): fn0 and fn1,
+// and fnd0 and fnd1, the same with WBC_STEP_DUALS (23: 48 multipliers per robot).
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -1775,7 +1776,9 @@ __device__ __forceinline__ void cn_face(const double* cnf, int p, double (&e)[3]
 // multiplier of every friction face and torque row to KernelArgs::dual: slot k < q of the
 // final working set holds its row id (act) and multiplier (u) in lane k; lane l owns rows l, 16 + l and
 // (l < 8) 32 + l, finds their slots by shuffling act and u over the twelve slots and writes each of its
-// rows once: the slot's u, 0 for a row outside the working set, 0 unless the status is OK
+// rows once: the slot's u, 0 for a row outside the working set, 0 unless the status is OK.  With FN (the
+// force-bound duals instances, wbc_kernel_fnd0.hip / wbc_kernel_fnd1.hip) the row stride is
+// WBC_DUAL_FORCE_LEN and lanes 8..15 own and write the force rows 32 + l as well
 // LM (with CN; the limits instances, wbc_kernel_lm0.hip / wbc_kernel_lm1.hip, KernelArgs::lm):
 // lmv holds what the lane's own rows need of its robot's limits row: the bound of torque row 16 + l
 // (joint l >> 1: tau_min on side 0, tau_max on side 1), of row 32 + l (joint 8 + (l & 7 >> 1)) and the mu
@@ -1802,7 +1805,7 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
                         double hws_tag = 0.0, [[maybe_unused]] const double* cnf = nullptr,
                         [[maybe_unused]] const double* lmv = nullptr, [[maybe_unused]] const double* fnv = nullptr) {
     static_assert(!LM || CN, "the limits instances are contact-normal instances");
-    static_assert(!FN || (LM && !DU && !OBJ), "the force-bound instances are limits instances without duals");
+    static_assert(!FN || (LM && !OBJ), "the force-bound instances are limits instances without an objective");
     constexpr int N = 12;
     constexpr int NTS = GEN ? 12 : NTS_ST;  // Nt row stride
     const wbc_params& pr = a.pv;
@@ -2555,6 +2558,17 @@ __device__ void solve16(const KernelArgs& a, int rb, int qp, int l, bool wr, con
             m1 = (ak == 16 + l) ? uk : m1;
             m2 = (ak == 32 + l) ? uk : m2;
         }
+        if constexpr (FN) {
+            // the 48-entry form (wbc.h WBC_DUAL_FORCE_LEN): lanes 8..15 own the force rows
+            // 32 + l = 40 + 2 leg + side in their third slot, so every lane stores three rows; a force row
+            // that does not exist never enters the working set and stores m2 = 0
+            if (wr) {
+                double* dr = a.dual + (size_t)qp * WBC_DUAL_FORCE_LEN;
+                dr[l] = ok ? m0 : 0.0;
+                dr[16 + l] = ok ? m1 : 0.0;
+                dr[32 + l] = ok ? m2 : 0.0;
+            }
+        } else
         if (wr) {
             double* dr = a.dual + (size_t)qp * WBC_DUAL_LEN;
             dr[l] = ok ? m0 : 0.0;
@@ -3885,7 +3899,8 @@ static_assert(offsetof(Presolve, presolved) == PRE_FLAG * sizeof(double), "PRE_F
 static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing");
 
 // OBJ: as solve16's (the objective from the recovered 42-vector, one entry per lane)
-// DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot)
+// DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot; with FN lane
+// r < 48, rows of 48)
 // LM: as build_normal's (KernelArgs::lm is null here when the QP's row is not accepted)
 template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
@@ -4480,11 +4495,27 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
         // The slot holding it carries its multiplier (slots >= q hold act = -1)
         const int lg = (lane >> 2) & 3;
         const int rank = __builtin_popcount(kap & ((1 << lg) - 1));
-        const int mine = (lane < 16) ? (((kap >> lg) & 1) ? mp.neq + 4 * rank + (lane & 3) : -2)
-                       : (lane < WBC_DUAL_LEN) ? mp.neq + mp.nfr + lane - 16 : -2;
+        int mine = (lane < 16) ? (((kap >> lg) & 1) ? mp.neq + 4 * rank + (lane & 3) : -2)
+                 : (lane < WBC_DUAL_LEN) ? mp.neq + mp.nfr + lane - 16 : -2;
+        if constexpr (FN) {
+            // the 48-entry form: lane 40 + 2 leg + side owns the leg's force row, constraint
+            // neq + nfr + ntq + 6 nsw + 2 (the leg's rank among the stance legs) + side of build_normal<CN, LM, FN>;
+            // no id for a leg in swing, for an infinite bound and for a table row the step does not accept
+            // (a.fn is null then), as build_normal leaves no constraint there
+            if (lane >= WBC_DUAL_LEN && lane < WBC_DUAL_FORCE_LEN) {
+                const int fl = (lane - WBC_DUAL_LEN) >> 1, side = lane & 1;
+                const int frank = __builtin_popcount(kap & ((1 << fl) - 1));
+                const double bd = a.fn ? a.fn[(size_t)rb * WBC_FN_LEN + (side ? WBC_FN_MAX : WBC_FN_MIN) + fl] : __builtin_inf();
+                const bool ex = ((kap >> fl) & 1) && fabs(bd) < __builtin_inf();
+                mine = ex ? mp.neq + mp.nfr + mp.ntq + 6 * mp.nsw + 2 * frank + side : -2;
+            }
+        }
         double mv = 0.0;
 #pragma unroll
         for (int k = 0; k < NQ; ++k) mv = (bcast_i(act, k) == mine) ? bcast(u, k) : mv;
+        if constexpr (FN) {
+            if (lane < WBC_DUAL_FORCE_LEN) a.dual[(size_t)rb * WBC_DUAL_FORCE_LEN + lane] = ok ? mv : 0.0;
+        } else
         if (lane < WBC_DUAL_LEN) a.dual[(size_t)rb * WBC_DUAL_LEN + lane] = ok ? mv : 0.0;
     }
     if (Hh) {  // working set for the next cycle's hotstart
@@ -5009,14 +5040,17 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18, FB_STEP_FND = 20 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_fn(int tag) { return tag >= FB_STEP_FN; }  // the force-bound instances (KernelArgs::fn), limits instances too
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
-// the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, and lmd0 / lmd1 under a limits table
-constexpr bool fb_writes_dual(int tag) { return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN); }
+// the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, lmd0 / lmd1 under a limits table, and
+// fnd0 / fnd1, the force-bound instances' (48 entries per robot: solve_phase<.., DU, LM, FN>)
+constexpr bool fb_writes_dual(int tag) {
+    return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN) || tag >= FB_STEP_FND;
+}
 constexpr bool fb_reads_lm(int tag) { return tag >= FB_STEP_LM; }  // the limits instances (KernelArgs::lm), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
 // does not accept (rp_bad_column) leaves the engine-wide values in place (its robot is flagged).
@@ -5069,7 +5103,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
 #pragma unroll
             for (int c = 0; c < WBC_FN_LEN; ++c) fv[c] = r[c];
             f.fn = fn_bad_column(fv) >= 0 ? nullptr : ka->fn;
-            solve_general_qp<true, false, false, true, true>(f, q1, *L);
+            solve_general_qp<true, false, fb_writes_dual(TAG), true, true>(f, q1, *L);
         } else {
         if constexpr (fb_reads_lm(TAG)) {
             // the fallback QP's own limits row: build_normal reads it where it stands; a row the step
@@ -5131,9 +5165,12 @@ constexpr bool STEP_DU = false;
 // the other rows are (lanes 8 + 2 leg and 9 + 2 leg hold fn_min and fn_max of one foot), and takes the unit
 // normal of that foot from the lane that holds its frame (lane 4 leg).  A null KernelArgs::lm leaves the
 // robot's own -+max_torque and friction in the limits' place.  A fallback callee of their own (FB_STEP_FN).
+// With WBC_STEP_DUALS (wbc_kernel_fnd0.hip, wbc_kernel_fnd1.hip) they are the instances of a
+// wbc_step with WBC_DUALS_FORCE: KernelArgs::dual is [B][WBC_DUAL_FORCE_LEN] for them, the 40 multipliers and
+// the force rows' 8 (solve16's DU under FN; FB_STEP_FND).
 template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false, bool FN = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
-    static_assert(!FN || (LM && !STEP_DU), "the force-bound instances are limits instances without duals");
+    static_assert(!FN || LM, "the force-bound instances are limits instances");
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
     static_assert(!STEP_DU || (BB && !SONLY), "the duals instances are base-body instances of any mask mix");
@@ -5367,7 +5404,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(FN ? FB_STEP_FN : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(FN ? (STEP_DU ? FB_STEP_FND : FB_STEP_FN) : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {

@@ -212,7 +212,9 @@ struct KernelArgs {
     // The multipliers of the friction and torque rows (wbc_step with WBC_DUALS): [batch][WBC_DUAL_LEN],
     // row qp for QP qp, in the hotstart's row numbering (wbc.h), zero where status is not WBC_QP_OK;
     // written only by the duals instances of the default step (wbc_kernel_du0.hip, wbc_kernel_du1.hip)
-    // and their fallback solve.  After obj, so that no other argument's offset moves.  (Keep the trailing
+    // and their fallback solve.  For the force-bound duals instances (wbc_kernel_fnd0.hip, wbc_kernel_fnd1.hip:
+    // wbc_step with WBC_DUALS_FORCE) the same member points at a buffer of [batch][WBC_DUAL_FORCE_LEN]:
+    // the stride is a compile-time constant of the instance.  After obj, so that no other argument's offset moves.  (Keep the trailing
     // comment on the declaration's own line: tests/test_modes_objective_cpu.py scans for lines ending in ';'
     // and expects obj to be the last of them)
     double* dual;       // [B][WBC_DUAL_LEN]
