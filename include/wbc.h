@@ -540,6 +540,42 @@ int32_t wbc_bind_device_force_bounds(wbc_engine* h, const double* d_table);
 /* The table in force, [B][WBC_FN_LEN] to the host (synchronous); without one (-inf x 4, +inf x 4). */
 int32_t wbc_get_force_bounds(wbc_engine* h, double* table);
 
+/* Per-robot reference contact forces, a force-tracking task in the QP's objective (a planner above the
+ * whole-body controller, an MPC say, computes reference ground-reaction forces and the step stays near
+ * them while it honours the dynamics, the cones and the actuators): a table of doubles, row-major
+ * [B][WBC_FT_LEN], row b for robot b.  Rows are 112 bytes, so a 16-byte-aligned table keeps aligned
+ * rows.  While a force-task table is in force the regulariser of every stance foot l of robot b changes
+ *     1/2 |f_l|^2   ->   1/2 w_b |f_l - fref_{b,l}|^2        (the constant dropped),
+ * fref in the world frame, in newtons, legs in the order LH, LF, RF, RH, w_b > 0 one weight per robot: in
+ * the reference's 42-variable QP the diagonal entries 18 + 3 l + k of a stance leg gain w - 1 and the
+ * gradient entries lose w fref[3 l + k].  Nothing else of the problem changes: the rows, their numbering
+ * in the hotstart and the multipliers are what they are without the table.  A swing foot's three fref
+ * entries are validated but not read, and its force stays 0.  The row (0 x 12, 1, 0), which
+ * wbc_get_force_task returns without a table, gives the step without the table bit for bit.  A row is
+ * invalid when an entry of columns 0-12 is not finite or weight <= 0. */
+enum {
+    WBC_FT_FREF = 0,    /* [12] reference force per foot (LH, LF, RF, RH), world frame, N */
+    WBC_FT_WEIGHT = 12, /* weight w of the robot's force task, > 0; 1: the plain regulariser's */
+    WBC_FT_LEN = 14     /* column 13 is reserved: ignored on input, 0 from wbc_get_force_task */
+};
+/* Host table, validated and then copied on the engine stream (the call synchronizes it).  An invalid
+ * row returns WBC_ERR_ARG, wbc_last_error names the row and the column, and the previous table stays
+ * in force.  NULL: back to no table of the engine's own (a bound device table stays in force).
+ * Supported under the table: the default wbc_step (stateless, stateful, WBC_COLD, WBC_DEBUG, WBC_NO_X,
+ * WBC_TIMED, WBC_GROUP) and the plain wbc_cycle, with any of the other per-robot tables in force.
+ * Refused with WBC_ERR_STATE: wbc_update, wbc_solve, wbc_step_modes, wbc_step / wbc_cycle with
+ * WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, and wbc_step with WBC_DUALS or WBC_DUALS_FORCE (no duals
+ * instance reads the table yet). */
+int32_t wbc_set_force_task(wbc_engine* h, const double* table);
+/* Caller-owned device table [B][WBC_FT_LEN] (no copy, no host validation; 16-byte aligned; a caller may
+ * rewrite it on the engine's stream every cycle, as a planner's forces are).  NULL restores the
+ * engine-owned table, or none.  On the device an invalid row gives that robot WBC_QP_NUMERIC and zero
+ * outputs; no other robot is touched. */
+int32_t wbc_bind_device_force_task(wbc_engine* h, const double* d_table);
+/* The table in force, [B][WBC_FT_LEN] to the host (synchronous), its reserved column 0; without one
+ * (0 x 12, 1, 0). */
+int32_t wbc_get_force_task(wbc_engine* h, double* table);
+
 /* One synchronous control cycle, host arrays in and out (the low-latency path for small batches,
  * e.g. the B = 1 drop-in of whole_body_controller_node): the inputs are packed into pinned staging
  * and sent in one H2D copy, the step runs (flags as wbc_step), and the outputs come back in one D2H

@@ -14,6 +14,8 @@ behind the C-ABI in include/wbc.h.  This package is the Python view of that C-AB
                   bind_device_limits / limits, limits_row;
                   per-foot bounds on the normal contact force (load ramps): Engine.set_force_bounds /
                   bind_device_force_bounds / force_bounds, force_bounds_row;
+                  per-robot reference contact forces (a force-tracking task in the QP's objective):
+                  Engine.set_force_task / bind_device_force_task / force_task, force_task_row;
                   contact-mode hypotheses (set_modes / step_modes) with each hypothesis' QP objective and the
                   best feasible one per state: flags OBJECTIVE / BEST, Engine.objective / best_modes;
                   which constraints bind: flag DUALS on step, Engine.duals / device_duals, dual_rows; under
@@ -32,10 +34,11 @@ from ._capi import (BEST, COLD, DEBUG, DUALS, DUALS_FORCE, DUAL_FORCE_LEN, FUSED
                     WbcModel, WbcParams, anymal_model, default_params, load_library, model_from_urdf, split_debug, Planner,
                     WbcPlannerParams, ROBOT_PARAM_NAMES, robot_param_table, contact_normal_table,
                     base_body_row, base_body_table, base_body_with_payload, dual_rows, limits_row, limits_table,
-                    force_bounds_row, force_bounds_table)
+                    force_bounds_row, force_bounds_table,
+                    force_task_row, force_task_table)
 
 __all__ = ["Engine", "Planner", "WbcPlannerParams", "model_from_urdf", "WbcError", "WbcModel", "WbcParams", "anymal_model", "default_params", "load_library",
            "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "OBJECTIVE", "BEST", "DUALS", "DUALS_FORCE", "DUAL_FORCE_LEN", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC",
            "ROBOT_PARAM_NAMES", "robot_param_table", "contact_normal_table",
            "base_body_row", "base_body_table", "base_body_with_payload", "dual_rows", "limits_row", "limits_table",
-           "force_bounds_row", "force_bounds_table"]
+           "force_bounds_row", "force_bounds_table", "force_task_row", "force_task_table"]

@@ -47,10 +47,16 @@ LIMIT_NAMES = ("tau_min", "tau_max", "friction")
 FN_LEN = 8
 FN_MIN, FN_MAX = 0, 4
 FORCE_BOUND_NAMES = ("fn_min", "fn_max")
+# the per-robot force-task table (WBC_FT_* in include/wbc.h): fref[12] (LH, LF, RF, RH; world frame, N), the
+# robot's weight > 0, one reserved column
+FT_LEN = 14
+FT_FREF, FT_WEIGHT = 0, 12
+FORCE_TASK_NAMES = ("f_ref", "weight")
 
 # the per-robot tables of the default step: name -> row length; the C entry points of table <name> are
 # wbc_set_<name>, wbc_bind_device_<name> and wbc_get_<name>
-TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN, "limits": LM_LEN, "force_bounds": FN_LEN}
+TABLES = {"robot_params": RP_LEN, "contact_normals": CN_LEN, "base_body": BB_LEN, "limits": LM_LEN, "force_bounds": FN_LEN,
+          "force_task": FT_LEN}
 TABLE_SYMBOLS = [f"wbc_{verb}_{name}" for name in TABLES for verb in ("set", "bind_device", "get")]
 # the objective and best-mode outputs of wbc_step_modes (WBC_OBJECTIVE / WBC_BEST)
 MODE_OUT_SYMBOLS = ["wbc_get_objective", "wbc_device_objective", "wbc_get_best_modes", "wbc_device_best_modes"]
@@ -461,6 +467,60 @@ def force_bounds_table(batch: int, defaults, table) -> np.ndarray:
     return np.ascontiguousarray(out)
 
 
+def force_task_row(f_ref=0.0, weight=1.0) -> np.ndarray:
+    """One (FT_LEN,) row of the force-task table: f_ref a scalar, (12,) or (4, 3) (feet LH, LF, RF, RH; world frame,
+    newtons), weight > 0; the defaults are the plain regulariser's row (0 x 12, 1, 0)."""
+    row = np.zeros(FT_LEN)
+    f = np.asarray(f_ref, np.float64)
+    if f.shape not in ((), (12,), (4, 3)):
+        raise ValueError(f"force task f_ref: need a scalar or shape (12,) or (4, 3), got {f.shape}")
+    row[FT_FREF:FT_WEIGHT] = f.reshape(-1) if f.shape else f
+    w = np.asarray(weight, np.float64)
+    if w.shape != ():
+        raise ValueError(f"force task weight: need a scalar, got shape {w.shape}")
+    row[FT_WEIGHT] = w
+    return row
+
+
+def force_task_bad_column(row) -> int:
+    """The validity rule of one force-task row (wbc_layout.h ft_bad_column): -1, or the first failing column: a
+    non-finite entry of f_ref or of the weight, weight <= 0.  The reserved column is not read."""
+    r = np.asarray(row, np.float64)
+    for c in range(FT_WEIGHT):
+        if not np.isfinite(r[FT_FREF + c]):
+            return FT_FREF + c
+    return FT_WEIGHT if not (np.isfinite(r[FT_WEIGHT]) and r[FT_WEIGHT] > 0.0) else -1
+
+
+def force_task_table(batch: int, defaults, table) -> np.ndarray:
+    """The [B, FT_LEN] table of wbc_set_force_task from a (B, 14) array, one (14,) row broadcast to all robots, or a
+    dict of FORCE_TASK_NAMES -> f_ref: a scalar, one (12,) or (4, 3) vector, a (B, 12) or (B, 4, 3) array; weight: a
+    scalar or a (B,) value per robot; missing entries take the rows of `defaults` ((B, 14): Engine.force_task()).
+    The engine validates it."""
+    B = int(batch)
+    out = np.array(np.broadcast_to(np.asarray(defaults, np.float64), (B, FT_LEN)))
+    if isinstance(table, dict):
+        unknown = sorted(set(table) - set(FORCE_TASK_NAMES))
+        if unknown:
+            raise ValueError(f"unknown force task entries {unknown}; entries are {FORCE_TASK_NAMES}")
+        if "f_ref" in table:
+            v = np.asarray(table["f_ref"], np.float64)
+            if v.shape not in ((), (12,), (4, 3), (B, 12), (B, 4, 3)):
+                raise ValueError(f"force task f_ref: need a scalar, shape (12,), (4, 3), ({B}, 12) or ({B}, 4, 3), got {v.shape}")
+            out[:, FT_FREF:FT_WEIGHT] = v.reshape(B, 12) if v.shape in ((B, 12), (B, 4, 3)) else (v.reshape(-1) if v.shape else v)
+        if "weight" in table:
+            v = np.asarray(table["weight"], np.float64)
+            if v.shape not in ((), (B,)):
+                raise ValueError(f"force task weight: need a scalar or shape ({B},), got {v.shape}")
+            out[:, FT_WEIGHT] = v
+    else:
+        t = np.asarray(table, np.float64)
+        if t.shape not in ((FT_LEN,), (B, FT_LEN)):
+            raise ValueError(f"force task table: need shape ({B}, {FT_LEN}) or ({FT_LEN},), got {t.shape}")
+        out[:, :] = t
+    return np.ascontiguousarray(out)
+
+
 class Engine:
     """A batch of B robots on one GPU (wraps wbc_engine*)."""
 
@@ -627,6 +687,27 @@ class Engine:
     def force_bounds(self) -> np.ndarray:
         """wbc_get_force_bounds: the [B, 8] table in force (without one: -inf x 4, +inf x 4 per robot)."""
         return self._get_table("force_bounds")
+
+    def set_force_task(self, table):
+        """wbc_set_force_task: per-robot reference contact forces for the default step: the regulariser of every
+        stance foot becomes weight / 2 |f - f_ref|^2 (a planner's forces, tracked softly; world frame, newtons).
+        `table`: a (B, 14) array, one (14,) row (force_task_row), or a dict {f_ref, weight} of scalars, (12,) /
+        (4, 3) vectors or per-robot arrays (force_task_table), whose missing entries keep what force_task()
+        returns now.  Validation is the engine's (WbcError names the row and column).  None clears the table."""
+        self._set_table("force_task", None if table is None else
+                        force_task_table(self.batch, self.force_task() if isinstance(table, dict) else 0.0, table))
+
+    def bind_device_force_task(self, table=0):
+        """wbc_bind_device_force_task: a caller-owned device table [B, 14] of doubles (no copy, no host
+        validation; it may be rewritten on the engine's stream every cycle, as a planner's forces are): an
+        integer device pointer, or an object with data_ptr() (a torch tensor), which the engine keeps referenced
+        while it is bound.  0 / None: the engine-owned table, or none."""
+        self._bind_table("force_task", table)
+
+    def force_task(self) -> np.ndarray:
+        """wbc_get_force_task: the [B, 14] table in force, its reserved column 0 (without one: 0 x 12, 1, 0 per
+        robot)."""
+        return self._get_table("force_task")
 
     def set_stream(self, stream):
         """Bind a caller stream: a torch.cuda.Stream (or any object with `cuda_stream`), which the engine

@@ -27,18 +27,19 @@ extern "C" hipError_t wbc_launch_solve_stance(const wbc::KernelArgs* a, hipStrea
 // The default step's launchers (wbc_launch_update_solve_<unit> of wbc_kernel_<unit>.hip), indexed by
 // wbc::StepInstance: kStepLaunchers[wbc::step_instance(...)] is a step's; the base-body units'
 // (WBC_STEP_UNITS_BB) follow the nine, the limits units' (WBC_STEP_UNITS_LM) those, the force-bound units'
-// (WBC_STEP_UNITS_FN) the limits units'
+// (WBC_STEP_UNITS_FN) the limits units', the force-task units' (WBC_STEP_UNITS_FT) the force-bound units'
 #define X(unit) extern "C" hipError_t wbc_launch_update_solve_##unit(const wbc::KernelArgs* a, hipStream_t st);
 WBC_STEP_UNITS(X)
 WBC_STEP_UNITS_BB(X)
 WBC_STEP_UNITS_LM(X)
 WBC_STEP_UNITS_FN(X)
+WBC_STEP_UNITS_FT(X)
 #undef X
 #define X(unit) wbc_launch_update_solve_##unit,
 static hipError_t (*const kStepLaunchers[])(const wbc::KernelArgs*, hipStream_t) = {WBC_STEP_UNITS(X) WBC_STEP_UNITS_BB(X) WBC_STEP_UNITS_LM(X)
-                                                                                       WBC_STEP_UNITS_FN(X)};
+                                                                                       WBC_STEP_UNITS_FN(X) WBC_STEP_UNITS_FT(X)};
 #undef X
-static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_LAUNCHER_COUNT, "one launcher per instance");
+static_assert(sizeof(kStepLaunchers) / sizeof(kStepLaunchers[0]) == wbc::STEP_LAUNCHER_COUNT_FT, "one launcher per instance");
 extern "C" hipError_t wbc_launch_modes(const wbc::KernelArgs* a, hipStream_t st);
 // the mode loop's objective instance (wbc_kernel_modes_obj.hip) and the selection after it (WBC_BEST)
 extern "C" hipError_t wbc_launch_modes_obj(const wbc::KernelArgs* a, hipStream_t st);
@@ -169,6 +170,10 @@ struct wbc_engine {
     // read them are limits and base-body instances; without a limits table in force they take each robot's
     // own -+max_torque and friction (a null KernelArgs::lm), the other tables as the limits kernels do
     RobotTable fn{WBC_FN_LEN};
+    // per-robot reference contact forces and their weight (KernelArgs::ft, [B][WBC_FT_LEN]; without: the plain
+    // regulariser).  The kernels that read them are force-bound instances: without a force-bound table in force
+    // their step reads d_fn_none, the other tables as the force-bound kernels do
+    RobotTable ft{WBC_FT_LEN};
     // bound (possibly external) inputs
     wbc::ConstInputView in{};
     // state / outputs
@@ -237,12 +242,14 @@ wbc::KernelArgs make_args(wbc_engine* h, uint32_t flags, const wbc::ConstInputVi
     a.params = h->d_params;
     a.limg = h->d_limg;
     a.pv = h->params;
-    const bool lf = h->lm.in_force || h->fn.in_force;  // limits or force bounds: their kernels read rp, cn and bb
+    // limits, force bounds or a force task: their kernels read rp, cn and bb
+    const bool lf = h->lm.in_force || h->fn.in_force || h->ft.in_force;
     a.rp = h->rp.in_force ? h->rp.in_force : ((h->cn.in_force || h->bb.in_force || lf) ? h->d_rp_uni : nullptr);
     a.cn = h->cn.in_force ? h->cn.in_force : ((h->bb.in_force || lf) ? h->d_cn_flat : nullptr);
     a.bb = h->bb.in_force ? h->bb.in_force : (lf ? h->d_bb_def : nullptr);
     a.lm = h->lm.in_force;
-    a.fn = h->fn.in_force;
+    a.fn = h->fn.in_force ? h->fn.in_force : (h->ft.in_force ? h->d_fn_none : nullptr);
+    a.ft = h->ft.in_force;
     a.base_pose = in.pose;
     a.nu = in.nu;
     a.qj = in.qj;
@@ -458,7 +465,7 @@ hipError_t launch_solves(wbc_engine* h, wbc::KernelArgs& a) {
 
 // The per-robot tables are read by the default wbc_step (and the plain wbc_cycle) only: with one in
 // force `call` is refused, outright (forms = 0) or when `flags` ask for one of `forms`.  The
-// parameter table is named before the normals, then the base bodies, the limits, the force bounds last; `allowed` says
+// parameter table is named before the normals, then the base bodies, the limits, the force bounds, the force task last; `allowed` says
 // what the call may still do.
 int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uint32_t forms, const char* allowed) {
     if (forms && !(flags & forms)) return WBC_OK;
@@ -469,6 +476,7 @@ int32_t refuse_tables(const wbc_engine* h, const char* call, uint32_t flags, uin
         {&wbc_engine::bb, "a per-robot base body table", " is in force", "it with wbc_set_base_body"},
         {&wbc_engine::lm, "per-robot limits", " are in force", "them with wbc_set_limits"},
         {&wbc_engine::fn, "per-foot force bounds", " are in force", "them with wbc_set_force_bounds"},
+        {&wbc_engine::ft, "a per-robot force task", " is in force", "it with wbc_set_force_task"},
     };
     for (const auto& t : kTables) {
         if (!(h->*t.table).in_force) continue;
@@ -637,7 +645,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
                     h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own, h->fn.own,
-                    h->d_dual48, h->d_fn_none};
+                    h->d_dual48, h->d_fn_none, h->ft.own};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -956,6 +964,34 @@ int32_t wbc_get_force_bounds(wbc_engine* h, double* table) {
     return table_get(h, &wbc_engine::fn, table, none);
 }
 
+static std::string ft_row_error(const double* row) {
+    const int c = wbc::ft_bad_column(row);
+    if (c < 0) return "";
+    char val[32];
+    std::snprintf(val, sizeof(val), "%g", row[c]);
+    const std::string name = c < WBC_FT_WEIGHT ? "f_ref[" + std::to_string(c / 3) + "][" + std::to_string(c % 3) + "]" : "weight";
+    return "column " + std::to_string(c) + " (" + name + ") = " + val + ": need finite f_ref and a finite weight > 0";
+}
+// The force-task kernels read every other table too: the engine's own parameter, normal, base-body and no-bounds
+// tables where none is in force, and a null limits table as the force-bound kernels take it
+static int32_t ensure_ft_tables(wbc_engine* h) {
+    if (const int32_t rc = ensure_rp_cn_bb_uniform(h)) return rc;
+    return ensure_fn_none(h);
+}
+static const double kPlainForceTask[WBC_FT_LEN] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+int32_t wbc_set_force_task(wbc_engine* h, const double* table) {
+    return table_set(h, &wbc_engine::ft, table, "wbc_set_force_task", "d_ft", ft_row_error, ensure_ft_tables);
+}
+int32_t wbc_bind_device_force_task(wbc_engine* h, const double* d_table) {
+    return table_bind(h, &wbc_engine::ft, d_table, "wbc_bind_device_force_task", ensure_ft_tables);
+}
+int32_t wbc_get_force_task(wbc_engine* h, double* table) {
+    if (!h || !table) return fail(WBC_ERR_ARG, "null argument");
+    if (const int32_t rc = table_get(h, &wbc_engine::ft, table, kPlainForceTask)) return rc;
+    for (size_t b = 0; b < (size_t)h->batch; ++b) table[b * WBC_FT_LEN + WBC_FT_LEN - 1] = 0.0;  // the reserved column
+    return WBC_OK;
+}
+
 int32_t wbc_reset(wbc_engine* h, const uint8_t* mask) {
     if (!h) return fail(WBC_ERR_ARG, "null handle");
     WBC_HIP(sync_own(h));
@@ -1018,6 +1054,10 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     if (duals && h->fn.in_force)
         return fail(WBC_ERR_STATE, "wbc_step: WBC_DUALS with per-foot force bounds in force (the 40 multipliers have no entry "
                                    "for a force row; clear them with wbc_set_force_bounds(h, NULL))");
+    if ((duals || dforce) && h->ft.in_force)
+        return fail(WBC_ERR_STATE, std::string("wbc_step: ") + (dforce ? "WBC_DUALS_FORCE" : "WBC_DUALS") +
+                                       " with a per-robot force task in force (no duals instance reads the table; clear it "
+                                       "with wbc_set_force_task(h, NULL))");
     if (dforce && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS_FORCE belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
     h->step_duals = wbc_engine::DUALS_NONE;
@@ -1055,7 +1095,8 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         // per-robot parameter table in force and under contact normals, which read the
         // parameter table too (the caller's, or the engine's uniform one), and under a
         // base-body table, which reads normals and parameters too; the stateless or the
-        // stateful one under a limits table, which reads all three
+        // stateful one under a limits table, which reads all three, under a force-bound table
+        //  and under a force-task table, which reads every other one
         WBC_HIP(begin_step16(h, a, flags, io.qmap));
         // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks; under
         // a limits table the limits units' own
@@ -1068,7 +1109,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_du1 : wbc_launch_update_solve_du0)(&a, h->stream));
         } else {
             WBC_HIP(kStepLaunchers[wbc::step_instance(a.cn != nullptr, a.rp != nullptr, step_all_stance(h, a), a.stateful != 0, a.bb != nullptr,
-                                                      a.lm != nullptr, a.fn != nullptr)](&a, h->stream));
+                                                      a.lm != nullptr, a.fn != nullptr, a.ft != nullptr)](&a, h->stream));
         }
     }
     if (timed) {

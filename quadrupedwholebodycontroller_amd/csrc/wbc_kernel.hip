@@ -11,6 +11,7 @@
 // argument LM (21): lm0 and lm1, and lmd0 and lmd1, the same with WBC_STEP_DUALS.
 // Two more hold the instances under per-foot normal-force bounds, a seventh template argument FN (22): fn0 and fn1,
 // and fnd0 and fnd1, the same with WBC_STEP_DUALS (23: 48 multipliers per robot).
+// Two more hold the instances under per-robot reference contact forces, an eighth template argument FT (24): ft0 and ft1.
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -671,8 +672,12 @@ __device__ __forceinline__ void g_row(const Prob& P, int i, double* grow) {
 // the slot Hessian H_s = I + Jc_com (I + Mbar_b^-2) Jc_com^T on stance slots (slack_weight I on
 // swing slots; lane i < 12 of the robot's segment holds row i) and the slot gradient
 // g_s = -Jc_com (W + [0, 0, g/m, 0, 0, 0]).
+// FT (the force-task instances' fallback, KernelArgs::ft): the identity of a stance slot is the
+// robot's weight ftw and the slot's gradient loses ftw * ftr, ftr the lane's own reference force entry.
+template <bool FT = false>
 __device__ __forceinline__ void slot_hessian_row(const Prob& P, int kap, const wbc_params& pr, int lane,
-                                                 double (&hrow)[12], double& gsv) {
+                                                 double (&hrow)[12], double& gsv, [[maybe_unused]] double ftw = 1.0,
+                                                 [[maybe_unused]] double ftr = 0.0) {
     const double inv_m = P.inv_m;
     const int i = lane < 12 ? lane : 11, li = i / 3, ri = i % 3;
     const bool sti = (kap >> li) & 1;
@@ -693,11 +698,14 @@ __device__ __forceinline__ void slot_hessian_row(const Prob& P, int kap, const w
 #pragma unroll
         for (int rj = 0; rj < 3; ++rj) {
             const int j = 3 * lj + rj;
-            const double h = (i == j ? 1.0 : 0.0) + (ri == rj ? ims : 0.0) + hc[rj];
+            double h;
+            if constexpr (FT) h = (i == j ? ftw : 0.0) + (ri == rj ? ims : 0.0) + hc[rj];
+            else h = (i == j ? 1.0 : 0.0) + (ri == rj ? ims : 0.0) + hc[rj];
             hrow[j] = (sti && stj) ? h : ((!sti && i == j) ? pr.slack_weight : 0.0);
         }
     }
     gsv = sti ? -(P.W[ri] + (ri == 2 ? pr.gravity * inv_m : 0.0) + dot3(ui, &P.W[3])) : 0.0;
+    if constexpr (FT) gsv = sti ? fma(-ftw, ftr, gsv) : gsv;
 }
 
 // Cholesky factor of a 12 x 12 SPD matrix (row i in lane i of the robot's segment, as hrow), its
@@ -819,10 +827,12 @@ __device__ bool factor12_rows(double (&hrow)[12], double gsv, int lane, double* 
 // Slot factorisation of the general solve: H_s, its factor, M = L^-1 and x0's slot part.  Runs
 // at the end of the update (four robots per wave in the update kernel) or, under mode
 // hypotheses, in the solve.  Returns false when H_s is not positive definite.
-template <int SUB>
+template <int SUB, bool FT = false>
 __device__ bool presolve(const Prob& P, int kap, const wbc_params& pr, int lane, double (&L)[12][13], double* ild,
-                         double* xs) {
+                         double* xs, [[maybe_unused]] double ftw = 1.0, [[maybe_unused]] double ftr = 0.0) {
     double hrow[12], gsv;
+    if constexpr (FT) slot_hessian_row<true>(P, kap, pr, lane, hrow, gsv, ftw, ftr);
+    else
     slot_hessian_row(P, kap, pr, lane, hrow, gsv);
     return factor12<SUB>(hrow, gsv, lane, L, ild, xs);
 }
@@ -857,10 +867,14 @@ __device__ __forceinline__ int seg16_argmax(double v) {
 // Lane i < 12 of the segment is row i = 3 l + k; SUB = 16 only (one robot per DPP row).
 // SOLVE (the update kernel's inline stance solve, wbc_update_solve_kernel): Nt, Y, q0, t0 and the
 // norms stay in the robot's LDS scratch (St16) instead of going to the Presolve record.
-template <bool SOLVE>
+// FT (the force-task instances, with SOLVE): g_f loses ftw * ftr, the robot's weight times the
+// lane's own reference force entry; the weight's part of H_f is rank6_factor's.
+template <bool SOLVE, bool FT = false>
 __device__ bool stance_reduce([[maybe_unused]] const KernelArgs& ka, [[maybe_unused]] int rb, const Prob& P,
                               const wbc_params& pr, int lane, bool wr, UpdScratch& s, double (&hrow)[12],
-                              double& gsv, Presolve* pre) {
+                              double& gsv, Presolve* pre, [[maybe_unused]] double ftw = 1.0,
+                              [[maybe_unused]] double ftr = 0.0) {
+    static_assert(!FT || SOLVE, "the force task belongs to the inline solve");
     auto& R = s.sr;
     const int i = lane < 12 ? lane : 11, l = i / 3, k = i % 3;
     const double dl[3] = {P.d[3 * l], P.d[3 * l + 1], P.d[3 * l + 2]};
@@ -1084,6 +1098,7 @@ __device__ bool stance_reduce([[maybe_unused]] const KernelArgs& ka, [[maybe_unu
         double cw[3];
         cross3(dl, &wv[3], cw);
         gsv = -(((k == 0) ? wv[0] : (k == 1) ? wv[1] : wv[2]) - ((k == 0) ? cw[0] : (k == 1) ? cw[1] : cw[2]));
+        if constexpr (FT) gsv = fma(-ftw, ftr, gsv);
     }
     UST(ka, rb, 13);  // Y, H_f row, g_f
     // Nt row j = (Mbj Y)_j Mb^-1 E^T + Jbj column j; t0_j = bbj_j + Mbj row j . q0.  Row kk of Y and
@@ -1160,7 +1175,13 @@ __device__ __forceinline__ void pk3(int k, const double* v, double* o) {  // row
     o[1] = (k == 0) ? v[2] : (k == 1) ? 0.0 : -v[0];
     o[2] = (k == 0) ? -v[1] : (k == 1) ? v[0] : 0.0;
 }
-__device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, double gsv, int lane) {
+// FT (the force-task instances): the identity of H_f is the robot's weight w = ftw, so
+// H_f = w (I - QQᵀ) + Q (w I + B) Qᵀ and, with w I + B = L6 L6ᵀ and c = ftc = w^(-1/2),
+// J0 = c I + Q (L6⁻ᵀ - c I) Qᵀ (the cross terms vanish: (I - QQᵀ) Q = 0).  w = 1 gives c = 1 exactly and
+// every product by c is exact, so the plain weight reproduces the bits of the code beside it.
+template <bool FT = false>
+__device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, double gsv, int lane,
+                                             [[maybe_unused]] double ftw = 1.0, [[maybe_unused]] double ftc = 1.0) {
     const int i = lane < 12 ? lane : 11, li = i / 3, ki = i % 3;
     double Hh[6][6];
 #pragma unroll
@@ -1240,7 +1261,8 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
 #pragma unroll
                 for (int m = a - 3; m < 3; ++m) t = fma(L22[m][a - 3], Xc[3 + m], t);
             }
-            Cc[a] = t + ((a == cc) ? 1.0 : 0.0);
+            if constexpr (FT) Cc[a] = t + ((a == cc) ? ftw : 0.0);
+            else Cc[a] = t + ((a == cc) ? 1.0 : 0.0);
         }
 #pragma unroll
         for (int a = 0; a < 6; ++a)
@@ -1299,6 +1321,7 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         double t = -Qi[c];
+        if constexpr (FT) t = -(ftc * Qi[c]);  // T = Liᵀ - c I
 #pragma unroll
         for (int r = 0; r <= c; ++r) t = fma(Qi[r], Li[c][r], t);
         ai[c] = t;
@@ -1319,7 +1342,8 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
         const double t = (k == 0) ? fma(bi[1], u[2], fma(-bi[2], u[1], ha[0]))
                        : (k == 1) ? fma(bi[2], u[0], fma(-bi[0], u[2], ha[1]))
                                   : fma(bi[0], u[1], fma(-bi[1], u[0], ha[2]));
-        J0[j] = (i == j) ? t + 1.0 : t;
+        if constexpr (FT) J0[j] = (i == j) ? t + ftc : t;
+        else J0[j] = (i == j) ? t + 1.0 : t;
     }
     // f0 = -J0 J0ᵀ g: Eᵀ v = [sum_l v_l, sum_l d_l x v_l]; q6 = L_G⁻¹ Eᵀ v
     auto q6_of = [&](double vv, double* q6) {
@@ -1348,11 +1372,13 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         double t = -q6[c];
+        if constexpr (FT) t = -(ftc * q6[c]);  // (FT: Tᵀ = Li - c I, and J0ᵀ g = c g + Q Tᵀ Qᵀ g)
 #pragma unroll
         for (int r = 0; r <= c; ++r) t = fma(Li[c][r], q6[r], t);
         w[c] = t;
     }
     double y = gsv;
+    if constexpr (FT) y = ftc * gsv;
 #pragma unroll
     for (int c = 0; c < 6; ++c) y = fma(Qi[c], w[c], y);
     q6_of(y, q6);
@@ -1360,11 +1386,13 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         double t = -q6[c];
+        if constexpr (FT) t = -(ftc * q6[c]);
 #pragma unroll
         for (int r = c; r < 6; ++r) t = fma(Li[r][c], q6[r], t);
         v[c] = t;
     }
     double f0 = y;
+    if constexpr (FT) f0 = ftc * y;  // (FT: J0 y = c y + Q T Qᵀ y)
 #pragma unroll
     for (int c = 0; c < 6; ++c) f0 = fma(Qi[c], v[c], f0);
     lds_sync();  // every lane has read Ĥ before the mirror overwrites it
@@ -1406,8 +1434,13 @@ __device__ __forceinline__ bool rank6_factor(const Prob& P, UpdScratch& s, doubl
 // swing legs' vacuous R1 rows (quirk A.12: 0 = r1).  Identical for every mask to the literal
 // 42 x 70 QP (oracle/wbc_reduced.py, tests/test_oracle_reduced.py).
 // ---------------------------------------------------------------------------------------
+// FT (the force-task instances): the identity d_aj of a stance slot is the robot's weight ftw (a swing
+// slot keeps 1, its joint-acceleration regulariser) and a stance slot's gradient loses ftw * ftr, ftr the lane's
+// own reference force entry.  The factor, N_t, t0, the rows and the map back to x are what they are without.
+template <bool FT = false>
 __device__ bool reduce_general([[maybe_unused]] const KernelArgs& ka, [[maybe_unused]] int rb, Prob& P,
-                               const wbc_params& pr, int lane, int kap, UpdScratch& s, const St16& V, bool& vac) {
+                               const wbc_params& pr, int lane, int kap, UpdScratch& s, const St16& V, bool& vac,
+                               [[maybe_unused]] double ftw = 1.0, [[maybe_unused]] double ftr = 0.0) {
     static_assert(offsetof(UpdScratch, sr) + offsetof(decltype(UpdScratch::sr), Y) >=
                       offsetof(UpdScratch, ps) + sizeof(UpdScratch::ps), "Y / q0 survive the factorisation");
     auto& R = s.sr;
@@ -1646,6 +1679,7 @@ __device__ bool reduce_general([[maybe_unused]] const KernelArgs& ka, [[maybe_un
                 cj[c] = seg_bcast<16>(Ci[c], j);
             }
             double h = (i == j) ? 1.0 : 0.0;
+            if constexpr (FT) h = (i == j) ? (sti ? ftw : 1.0) : 0.0;
             if (!sti && j / 3 == l) h = fma(wsw, sel3d(j % 3, blk[0], blk[1], blk[2]), h);
             double t1 = 0.0, ta = 0.0, tb = 0.0;  // both dots, one select (not one per component)
 #pragma unroll
@@ -1666,6 +1700,7 @@ __device__ bool reduce_general([[maybe_unused]] const KernelArgs& ka, [[maybe_un
 #pragma unroll
         for (int c = 0; c < 6; ++c) ew = fma(Ei[c], wv[c], ew);
         gsv = (sti ? -ew : wsw * gown) + gam;
+        if constexpr (FT) gsv = sti ? fma(-ftw, ftr, gsv) : gsv;
     }
     UST(ka, rb, 22);
     // R7: H = L L^T, M = L^-1, x0 = -H^-1 g (ps.L, ps.xs: over W .. Si, all read by now)
@@ -2634,13 +2669,19 @@ __device__ __forceinline__ void leg_bounds(double kr1, double ksw, double ko, do
 }
 
 template <int SUB, bool SOLVE = false, typename Model = wbc_model, bool MLOOP = false, int STF = -1, bool SONLY = false,
-          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
+          bool RP = false, bool CN = false, bool BB = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false,
+          bool FT = false>
 __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp, int kap, int lane, bool wr, UpdScratch& s, Prob& P,
                              Presolve* pre, const Model& md, const double* fric = nullptr,
                              const double* vin = nullptr, int chunk = 0, unsigned* fails = nullptr,
                              [[maybe_unused]] const double* cnf = nullptr, [[maybe_unused]] const double* bbr = nullptr,
-                             [[maybe_unused]] const double* lmv = nullptr, [[maybe_unused]] const double* fnv = nullptr) {
+                             [[maybe_unused]] const double* lmv = nullptr, [[maybe_unused]] const double* fnv = nullptr,
+                             [[maybe_unused]] const double* ftv = nullptr) {
+    static_assert(!FT || FN, "the force-task instances are force-bound instances");
     const wbc_params& pr = a.pv;
+    // FT (the force-task instances, KernelArgs::ft): ftv is the lane's reference force entry (lane i < 12: fref_i),
+    // the robot's weight w and c = w^(-1/2), handed to the two reductions (and the rank-6 factor); solve16 and the
+    // pass read none of them
     // FN (the force-bound instances, KernelArgs::fn): fnv is the lane's bound and its row's unit normal, handed
     // on to solve16 as lmv is
     // LM (the limits instances, KernelArgs::lm): lmv is the lane's share of its robot's limits row, handed
@@ -3491,6 +3532,14 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         // knows): the stance form only, the general form compiled out
         if (SONLY || (!stateful && kap == 15)) {
             double hrow[12], gsv = 0.0;
+            if constexpr (FT) {
+                if (stance_reduce<true, true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr, ftv[1], ftv[0]) &&
+                    rank6_factor<true>(P, s, gsv, lane, ftv[1], ftv[2])) {
+                    solve16<true, false, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf, lmv, fnv);
+                    return true;
+                }
+                return false;
+            }
             if (stance_reduce<true>(a, rb, P, pr, lane, wr, s, hrow, gsv, nullptr) && rank6_factor(P, s, gsv, lane)) {
                 UST(a, rb, 11);
                 if constexpr (FN) solve16<true, false, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, St16(s, fric), 15, WBC_QP_OK, 0.0, 0.0, 0.0, cnf, lmv, fnv);
@@ -3503,6 +3552,14 @@ __device__ __forceinline__ bool update_phase(const KernelArgs& a, int rb, int qp
         if constexpr (SONLY) return false;
         const St16 V(s, P, fric);
         bool vac = false;
+        if constexpr (FT) {
+            if (reduce_general<true>(a, rb, P, pr, lane, kap, s, V, vac, ftv[1], ftv[0])) {
+                solve16<true, true, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
+                                                                      hWlo, hWhi, hWtag, cnf, lmv, fnv);
+                return true;
+            }
+            return false;
+        }
         if (reduce_general(a, rb, P, pr, lane, kap, s, V, vac)) {
             UST(a, rb, 11);
             if constexpr (FN) solve16<true, true, STF, RP, CN, false, DU, LM, true>(a, rb, qp, lane, wr, P, s, V, kap, vac ? WBC_QP_INFEASIBLE : WBC_QP_OK,
@@ -3902,7 +3959,9 @@ static_assert(offsetof(Presolve, xs) == 78 * sizeof(double), "Presolve packing")
 // DU: as solve16's (lane r < 40 owns row r of KernelArgs::dual and finds its constraint's slot; with FN lane
 // r < 48, rows of 48)
 // LM: as build_normal's (KernelArgs::lm is null here when the QP's row is not accepted)
-template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
+// FT: the slot Hessian and gradient under row rb of KernelArgs::ft (slot_hessian_row<true>; null here when the QP's
+// row is not accepted: the plain regulariser, its robot is flagged)
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false, bool FT = false>
 __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const PreRegs* pf, QpScratch& s) {
     const wbc_params& pr = a.pv;
     const int lane = lane_id();
@@ -3948,6 +4007,15 @@ __device__ void solve_phase(const KernelArgs& a, int rb, const Prob& P, const Pr
             const int i = k / 12, j = k % 12;
             if (j > i) s.Mi()[i][j] = 0.0;
         }
+    } else if constexpr (FT) {
+        // (the force-task fallback never comes presolved: drain_fallbacks' records carry presolved = 0)
+        double ftw = 1.0, ftr = 0.0;
+        if (a.ft) {
+            const double* r = a.ft + (size_t)rb * WBC_FT_LEN;
+            ftw = r[WBC_FT_WEIGHT];
+            ftr = r[WBC_FT_FREF + (lane < 12 ? lane : 11)];
+        }
+        if (!presolve<64, true>(P, kap, pr, lane, s.L, s.ild, s.xs, ftw, ftr) && status == WBC_QP_OK) status = WBC_QP_NUMERIC;
     } else if (!presolve<64>(P, kap, pr, lane, s.L, s.ild, s.xs) && status == WBC_QP_OK) {
         status = WBC_QP_NUMERIC;
     }
@@ -5031,7 +5099,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_kernel(KernelArgs a) {
 // problem to work row qp (no slot factor: presolved = 0), which the same wave then solves with the
 // general 24-variable method (drain_fallbacks, modes = 0: the record carries the QP's own mask and
 // masked bounds).
-template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false>
+template <bool CN = false, bool OBJ = false, bool DU = false, bool LM = false, bool FN = false, bool FT = false>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update scratch");
 // A call (the rare path stays out of the kernel's register allocation), handed the address of the
@@ -5040,16 +5108,17 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18, FB_STEP_FND = 20 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18, FB_STEP_FND = 20, FB_STEP_FT = 22 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_fn(int tag) { return tag >= FB_STEP_FN; }  // the force-bound instances (KernelArgs::fn), limits instances too
+constexpr bool fb_reads_ft(int tag) { return tag >= FB_STEP_FT; }  // the force-task instances (KernelArgs::ft), force-bound instances too
 constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-robot-parameter and contact-normal instances
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
 // the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, lmd0 / lmd1 under a limits table, and
 // fnd0 / fnd1, the force-bound instances' (48 entries per robot: solve_phase<.., DU, LM, FN>)
 constexpr bool fb_writes_dual(int tag) {
-    return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN) || tag >= FB_STEP_FND;
+    return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN) || (tag >= FB_STEP_FND && tag < FB_STEP_FT);
 }
 constexpr bool fb_reads_lm(int tag) { return tag >= FB_STEP_LM; }  // the limits instances (KernelArgs::lm), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
@@ -5103,6 +5172,15 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
 #pragma unroll
             for (int c = 0; c < WBC_FN_LEN; ++c) fv[c] = r[c];
             f.fn = fn_bad_column(fv) >= 0 ? nullptr : ka->fn;
+            if constexpr (fb_reads_ft(TAG)) {
+                // and its force-task row: one the step does not accept leaves the plain regulariser
+                const double* t = ka->ft + (size_t)q1 * WBC_FT_LEN;
+                double tv[WBC_FT_LEN - 1];
+#pragma unroll
+                for (int c = 0; c < WBC_FT_LEN - 1; ++c) tv[c] = t[c];
+                f.ft = ft_bad_column(tv) >= 0 ? nullptr : ka->ft;
+                solve_general_qp<true, false, false, true, true, true>(f, q1, *L);
+            } else
             solve_general_qp<true, false, fb_writes_dual(TAG), true, true>(f, q1, *L);
         } else {
         if constexpr (fb_reads_lm(TAG)) {
@@ -5168,8 +5246,16 @@ constexpr bool STEP_DU = false;
 // With WBC_STEP_DUALS (wbc_kernel_fnd0.hip, wbc_kernel_fnd1.hip) they are the instances of a
 // wbc_step with WBC_DUALS_FORCE: KernelArgs::dual is [B][WBC_DUAL_FORCE_LEN] for them, the 40 multipliers and
 // the force rows' 8 (solve16's DU under FN; FB_STEP_FND).
-template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false, bool FN = false>
+// FT (with FN, LM, BB, CN and RP): the force-task instances (wbc_kernel_ft0.hip, wbc_kernel_ft1.hip; DESIGN.md
+// 24): each lane loads, with its inputs, its share of row qp of KernelArgs::ft, indexed as the other rows are:
+// lane i < 12 the reference force entry fref_i, every lane the weight w.  The two reductions put w on the
+// diagonal of a stance slot and subtract w fref_i from its gradient; solve16 and the pass are the force-bound
+// instances'.  A fallback callee of their own (FB_STEP_FT).
+template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false, bool FN = false,
+          bool FT = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
+    static_assert(!FT || FN, "the force-task instances are force-bound instances");
+    static_assert(!FT || !STEP_DU, "no duals instance reads the force task");
     static_assert(!FN || LM, "the force-bound instances are limits instances");
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
@@ -5282,6 +5368,15 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
         const double w = a.fn[(size_t)qp * WBC_FN_LEN + (lane >= 8 ? (lane & 1) * 4 + ((lane - 8) >> 1) : 0)];
         fnv[0] = lane >= 8 ? w : ((lane & 1) ? __builtin_inf() : -__builtin_inf());
     }
+    // the lane's share of the QP's force-task row in the same batch (two 8-byte loads): lane i < 12 the
+    // reference force entry fref_i (lanes 12..15 reload entry 11 and never use it), every lane the weight;
+    // ftv[2] is c = w^(-1/2), formed below
+    [[maybe_unused]] double ftv[3] = {0.0, 1.0, 1.0};
+    if constexpr (FT) {
+        const double* r = a.ft + (size_t)qp * WBC_FT_LEN;
+        ftv[0] = r[WBC_FT_FREF + (lane < 12 ? lane : 11)];
+        ftv[1] = r[WBC_FT_WEIGHT];
+    }
     // the model and friction table: the host-built LDS image (wbc_layout.h), one contiguous copy (the
     // limits instances: the model alone)
     static_assert(offsetof(LdsImage, fric) == (LIMG_LEN - FRIC_LEN) * sizeof(double), "the friction table ends the image");
@@ -5329,6 +5424,18 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
                 fnv[0] = hi ? __builtin_inf() : -__builtin_inf();
             }
         }
+        if constexpr (FT) {
+            // the force-task row's validity (ft_bad_column's two entry rules on what the lanes hold).  A row the
+            // step does not accept flags the robot as a bad parameter row does and leaves the plain regulariser.
+            // c = w^(-1/2) with the correctly rounded square root and division: w = 1 gives exactly 1
+            const bool tbad = seg_any<UPD_SUB>(ft_fref_bad(ftv[0]) || ft_weight_bad(ftv[1]));
+            if (tbad) {
+                vin[0] = __builtin_nan("");
+                ftv[0] = 0.0;
+                ftv[1] = 1.0;
+            }
+            ftv[2] = 1.0 / __builtin_sqrt(ftv[1]);
+        }
         if constexpr (LM) {
             // the row's validity (lm_bad_column's two entry rules on what the lanes hold: lanes 2 j and
             // 2 j + 1 hold tau_min and tau_max of joint j, and of joint 8 + j in the second slot; every mu is
@@ -5374,7 +5481,10 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
                 if (bbad) vin[0] = __builtin_nan("");
                 if (bbad) bbr = &L.model.base_mass;
             }
-            if constexpr (FN)
+            if constexpr (FT)
+            solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU, LM, true, true>(
+                ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr, lmv, fnv, ftv);
+            else if constexpr (FN)
             solved = update_phase<UPD_SUB, true, LdsModel, false, STF, SONLY, true, true, BB, false, STEP_DU, LM, true>(
                 ar, row, qp, kap, lane, wr, L.u[seg], L.prob[seg], nullptr, L.model, &L.fric[0], vin, 0, nullptr, cnf, bbr, lmv, fnv);
             else
@@ -5404,7 +5514,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(FN ? (STEP_DU ? FB_STEP_FND : FB_STEP_FN) : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(FT ? FB_STEP_FT : FN ? (STEP_DU ? FB_STEP_FND : FB_STEP_FN) : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {
@@ -5578,7 +5688,7 @@ __device__ __forceinline__ int qp_mask(const KernelArgs& a, int rb, int row) {
     return a.modes ? (a.mode_masks[rb - row * a.modes] & 15) : (a.contacts[rb] & 15);
 }
 
-template <bool CN, bool OBJ, bool DU, bool LM, bool FN>
+template <bool CN, bool OBJ, bool DU, bool LM, bool FN, bool FT>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L);
 
 #ifndef WBC_SINGLE_TU
@@ -5605,7 +5715,7 @@ WBC_KERNEL_ATTR void wbc_solve_fallback_kernel(KernelArgs a) {
 
 #endif  // WBC_SINGLE_TU
 
-template <bool CN, bool OBJ, bool DU, bool LM, bool FN>
+template <bool CN, bool OBJ, bool DU, bool LM, bool FN, bool FT>
 __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
     // mode hypotheses: QP rb is hypothesis rb % modes of state rb / modes (one assembled problem
     // per state, read by all of its hypotheses)
@@ -5632,7 +5742,7 @@ __device__ void solve_general_qp(const KernelArgs& a, int rb, SolveLds& L) {
         if (lane == 0) L.prob.kappa = (double)kap;
     }
     wsync();
-    solve_phase<CN, OBJ, DU, LM, FN>(a, rb, L.prob, &pf, L.q);
+    solve_phase<CN, OBJ, DU, LM, FN, FT>(a, rb, L.prob, &pf, L.q);
 }
 
 #ifndef WBC_SINGLE_TU
@@ -5877,7 +5987,7 @@ __global__ void wbc_reset_kernel(double* hist, const uint8_t* mask, int batch) {
 }  // namespace wbc
 
 #ifdef WBC_STEP_INSTANCE
-// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB[, LM[, FN]]]>, in a translation unit
+// An instance of the default step, wbc_update_solve_kernel<STF, SONLY, RP, CN[, BB[, LM[, FN[, FT]]]]>, in a translation unit
 // of its own so that its schedule can be chosen apart from the other kernels' (Makefile <UNIT>_KFLAGS):
 // the unit file names the launcher and the template arguments, the engine picks the launcher
 // (wbc_engine.cpp kStepLaunchers, wbc_layout.h step_instance).  The step in one launch: the update

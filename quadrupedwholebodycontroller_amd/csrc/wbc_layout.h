@@ -234,6 +234,13 @@ struct KernelArgs {
     // the limits' place.  Last, so that no other argument's offset moves.  (The block comment stays behind
     // the declaration, as lm's.)
     const double* fn; /* [B][WBC_FN_LEN] */
+    // Per-robot reference contact forces and their weight (wbc_set_force_task / wbc_bind_device_force_task):
+    // [batch][WBC_FT_LEN], row qp for QP qp (fref[12], weight, one reserved; ft_bad_column below); read only by
+    // the force-task instances of the default step (wbc_kernel_ft0.hip, wbc_kernel_ft1.hip), which are instances
+    // of every other table too: the engine points fn, bb, cn and rp at tables of its own where none is in force,
+    // and a null lm is taken as the force-bound instances take it.  Last, so that no other argument's offset
+    // moves.  (The block comment stays behind the declaration, as lm's.)
+    const double* ft; /* [B][WBC_FT_LEN] */
 };
 
 // ---------------------------------------------------------------------------------------
@@ -267,13 +274,16 @@ WBC_HD inline int rp_bad_column(const double* r) {
 // forms take the flags in the template's order (a unit's WBC_STEP_INSTANCE).
 // FN (the force-bound instances, a seventh, false for every earlier unit): no force-bound table; such an
 // instance takes a null limits table (each robot's own -+max_torque and friction stand).
+// FT (the force-task instances, an eighth, false for every earlier unit): no force-task table; such an
+// instance is a force-bound instance too (the engine's own no-bounds table where none is in force).
 inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, const KernelArgs& a, bool BB = false, bool LM = false,
-                              bool FN = false) {
+                              bool FN = false, bool FT = false) {
     if (a.nwaves <= 0 || (a.stateful != 0) != (STF != 0)) return true;
     if (SONLY && (a.modes || a.qmap)) return true;
     if (RP && (a.modes || !a.rp)) return true;
     if (CN && !a.cn) return true;
     if (BB && !a.bb) return true;
+    if (FT && !a.ft) return true;
     if (FN) return !a.fn;
     return LM && !a.lm;
 }
@@ -285,6 +295,9 @@ inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bo
 }
 inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bool LM, bool FN, const KernelArgs& a) {
     return step_args_refused(STF, SONLY, RP, CN, a, BB, LM, FN);
+}
+inline bool step_args_refused(int STF, bool SONLY, bool RP, bool CN, bool BB, bool LM, bool FN, bool FT, const KernelArgs& a) {
+    return step_args_refused(STF, SONLY, RP, CN, a, BB, LM, FN, FT);
 }
 // The default step's instances, one kernel unit each (wbc_kernel_<unit>.hip): per table in force
 // (none, parameters, parameters + normals; parameters + normals + base bodies in the second list
@@ -336,8 +349,22 @@ enum StepInstanceFN {
 #undef X
     STEP_LAUNCHER_COUNT
 };
-constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false, bool lm = false, bool fn = false) {
-    return fn ? (stateful ? (int)STEP_fn1 : (int)STEP_fn0)
+// The force-task instances (KernelArgs::ft), in a fifth list whose values go on from
+// STEP_LAUNCHER_COUNT (which keeps its value): the launcher table has STEP_LAUNCHER_COUNT_FT entries, built
+// from the five lists in this order.  ft wins over every other table; no stance-only unit: an all-stance
+// step runs ft0, whose mask-15 waves take the stance form.
+#define WBC_STEP_UNITS_FT(X) X(ft0) X(ft1)
+enum StepInstanceFT {
+    STEP_FT_FIRST_ = STEP_LAUNCHER_COUNT - 1,
+#define X(unit) STEP_##unit,
+    WBC_STEP_UNITS_FT(X)
+#undef X
+    STEP_LAUNCHER_COUNT_FT
+};
+constexpr int step_instance(bool cn, bool rp, bool all_stance, bool stateful, bool bb = false, bool lm = false, bool fn = false,
+                            bool ft = false) {
+    return ft ? (stateful ? (int)STEP_ft1 : (int)STEP_ft0)
+         : fn ? (stateful ? (int)STEP_fn1 : (int)STEP_fn0)
          : lm ? (stateful ? (int)STEP_lm1 : (int)STEP_lm0)
          : bb ? (all_stance ? (int)STEP_bbs : stateful ? (int)STEP_bb1 : (int)STEP_bb0)
          : all_stance ? (cn ? STEP_cns : rp ? STEP_rps : STEP_stance)
@@ -478,6 +505,18 @@ WBC_HD inline int fn_bad_column(const double* r) {
         if (c >= WBC_FN_MAX && (r[c] != r[c] || fn_pair_bad(r[c - WBC_FN_MAX + WBC_FN_MIN], r[c]))) return c;
     }
     return -1;
+}
+// A force-task row (wbc.h WBC_FT_*: fref[12], weight, one reserved) the step accepts: -1, or the first column
+// that fails: a non-finite entry in columns 0-12 at its own column, weight <= 0 at the weight's.  The reserved
+// column is not read.  One definition for the host's validation (wbc_set_force_task) and the kernels' (a
+// device-bound row): the kernels hold fref_i in lane i < 12 and the weight in every lane and apply the two
+// entry rules, ft_fref_bad and ft_weight_bad, to what each lane holds.
+WBC_HD inline bool ft_fref_bad(double f) { return !__builtin_isfinite(f); }
+WBC_HD inline bool ft_weight_bad(double w) { return !__builtin_isfinite(w) || !(w > 0.0); }
+WBC_HD inline int ft_bad_column(const double* r) {
+    for (int c = 0; c < WBC_FT_WEIGHT; ++c)
+        if (ft_fref_bad(r[WBC_FT_FREF + c])) return WBC_FT_FREF + c;
+    return ft_weight_bad(r[WBC_FT_WEIGHT]) ? WBC_FT_WEIGHT : -1;
 }
 WBC_HD inline int32_t qmap_entry(int qp, int mask) { return (int32_t)((qp << 4) | (mask & 15)); }
 constexpr int QMAP_SEG = 4;  // QPs per wave (UPD_RPW of the kernel)

@@ -8,7 +8,7 @@ per VALU instruction at one wave per SIMD) from latency-bound one
 Usage: python tools/isa_stages.py [listing.s] [source.hip] [--sym NAME]
 (make -C quadrupedwholebodycontroller_amd/csrc build/wbc_kernel_stance.s; the default symbol is the
 stance-only stateless instance of that unit, wbc_update_solve_kernel<0, true, false>; the mixed-form
-instance of build/wbc_kernel_step0.s is --sym _ZN3wbc23wbc_update_solve_kernelILi0ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_10KernelArgsE)"""
+instance of build/wbc_kernel_step0.s is --sym _ZN3wbc23wbc_update_solve_kernelILi0ELb0ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_10KernelArgsE)"""
 import collections
 import os
 import re
@@ -16,7 +16,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrupedwholebodycontroller_amd", "csrc")
-SYM = "_ZN3wbc23wbc_update_solve_kernelILi0ELb1ELb0ELb0ELb0ELb0ELb0EEEvNS_10KernelArgsE"  # the stance-only stateless instance
+SYM = "_ZN3wbc23wbc_update_solve_kernelILi0ELb1ELb0ELb0ELb0ELb0ELb0ELb0EEEvNS_10KernelArgsE"  # the stance-only stateless instance
 # a device function's first line, with or without __forceinline__
 FN = r"^__device__ (__forceinline__ )?%s %s\("
 
