@@ -128,6 +128,8 @@ COLD_SETS = {
 TABLES_SET = "tables_16"
 TROT_SET = "trot_8x30_40Nm"
 TROT = dict(B=8, steps=30, seed=2, max_torque=40.0)
+# the mask-change cycles of the limits step off the trot (tests/offtrot_tables_oracle.py, lmd1): set -> latched
+OFFTROT_SETS = {"offtrot_lm_latched": True, "offtrot_lm_unlatched": False}
 _CACHE = {}
 
 
@@ -174,6 +176,13 @@ def trot_set():
     return _CACHE[TROT_SET]
 
 
+def offtrot_set(name):
+    """The Snapshots (70-row QPs) of offtrot_tables_oracle's limits run on its 256 mask-change cycles, B = 4."""
+    import offtrot_tables_oracle as OT  # (it imports this module through the oracles' chain)
+
+    return OT.snapshots("lm", OFFTROT_SETS[name])
+
+
 class Snapshot:
     """What `expand` and `certificate` read of a controller, kept after the controller has stepped on."""
 
@@ -200,6 +209,8 @@ def measure():
     """{"stationarity": {set: worst}, "primal": {set: worst}} of the numpy oracle on its own x."""
     res = {name: oracle_residual(cold_set(name)[2]) for name in (*COLD_SETS, TABLES_SET)}
     res[TROT_SET] = oracle_residual([c for row in trot_set()[1] for c in row])
+    for name in OFFTROT_SETS:
+        res[name] = oracle_residual(offtrot_set(name))
     return {kind: {name: v[i] for name, v in res.items()} for i, kind in enumerate(KINDS)}
 
 

@@ -146,7 +146,9 @@ COLD_SETS = ("stance_cold_64", "rl_random_61", "straight_5")  # force_bounds_ora
 TABLES_SET = "five_tables_16"
 RAMP_SET = "ramp_8x130"
 DIRECT_SET = "direct_point_8x3"
-ALL_SETS = (*COLD_SETS, TABLES_SET, RAMP_SET, DIRECT_SET)
+# the mask-change cycles of the force-bound step off the trot (tests/offtrot_tables_oracle.py, fnd1): set -> latched
+OFFTROT_SETS = {"offtrot_fn_latched": True, "offtrot_fn_unlatched": False}
+ALL_SETS = (*COLD_SETS, TABLES_SET, RAMP_SET, DIRECT_SET, *OFFTROT_SETS)
 _CACHE = {}
 
 
@@ -241,6 +243,10 @@ def controllers(name):
         return [c for row in ramp_snapshots()[1] for c in row]
     if name == DIRECT_SET:
         return [c for row in direct_point_set()[2] for c in row]
+    if name in OFFTROT_SETS:
+        import offtrot_tables_oracle as OT  # (it imports this module for Snapshot)
+
+        return OT.snapshots("fn", OFFTROT_SETS[name])
     return cold_set(name)[2]
 
 
