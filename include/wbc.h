@@ -135,6 +135,9 @@ enum {
 #define WBC_DUALS_FORCE 4096u /* wbc_step only (default form), implies WBC_DUALS: the same 40 multipliers and the 8 of
                           * the per-foot normal-force bounds, 48 per robot (wbc_get_force_duals /
                           * wbc_device_force_duals); allowed with and without a force-bound table in force */
+#define WBC_DUALS_TASK 8192u /* wbc_step only (default form), implies WBC_DUALS_FORCE: the same 48 multipliers under a
+                          * per-robot force task (wbc_set_force_task), read with the same two getters; allowed
+                          * with and without a force-task table in force */
 
 /* Debug record layout (doubles per robot), written by update/step under WBC_DEBUG. */
 enum {
@@ -293,6 +296,23 @@ int32_t wbc_device_duals(wbc_engine* h, double** d_dual);
  * unless the last wbc_step carried WBC_DUALS_FORCE, and after such a step wbc_get_duals / wbc_device_duals
  * return WBC_ERR_STATE.  WBC_DUALS_FORCE with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, or on wbc_update /
  * wbc_solve / wbc_cycle / wbc_step_modes, is WBC_ERR_ARG. */
+/* Under a per-robot force task (wbc_set_force_task below) the flag is WBC_DUALS_TASK: wbc_step(flags |
+ * WBC_DUALS_TASK) in its default form writes the same [B][WBC_DUAL_FORCE_LEN] vector in the same numbering into
+ * the same buffer, read with the same two getters (after such a step they succeed, and wbc_get_duals /
+ * wbc_device_duals return WBC_ERR_STATE as after WBC_DUALS_FORCE).  The multipliers are those of the QP the
+ * step solves: the 74-row problem whose diagonal entries 18 + 3 l + k of a stance leg carry w and whose
+ * gradient entries lose w fref[3 l + k].  The task changes H and g and no row, so the elimination argument
+ * above holds word for word; what changes is the scale: lambda is in units of the objective per row unit, and
+ * the objective's force part is 1/2 w |f - fref|^2, so the multipliers grow with w (a row that keeps a foot
+ * from its reference force prices a newton at about w times the distance to the reference).  The flag implies
+ * WBC_DUALS_FORCE (that bit and WBC_DUALS' are ignored beside it); the two older flags keep their refusals
+ * while a force-task table is in force.  Allowed as WBC_DUALS_FORCE is, with any combination of the six
+ * per-robot tables, the force task included, and without a force-task table: then the step runs under the
+ * engine's own table of (0 x 12, 1, 0) rows (built at the first such step, freed by wbc_destroy) and all 48
+ * entries, tau, grf, x, status and iters are WBC_DUALS_FORCE's bits, so a caller who switches the task on and
+ * off keeps one code path.  Under a table, tau, grf, x, status and iters are bit-identical to the step without
+ * the flag.  WBC_DUALS_TASK with WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, or on wbc_update / wbc_solve /
+ * wbc_cycle / wbc_step_modes, is WBC_ERR_ARG. */
 enum { WBC_DUAL_FORCE_LEN = 48 };
 int32_t wbc_get_force_duals(wbc_engine* h, double* dual /* [B][48] */);
 int32_t wbc_device_force_duals(wbc_engine* h, double** d_dual);
@@ -564,8 +584,9 @@ enum {
  * Supported under the table: the default wbc_step (stateless, stateful, WBC_COLD, WBC_DEBUG, WBC_NO_X,
  * WBC_TIMED, WBC_GROUP) and the plain wbc_cycle, with any of the other per-robot tables in force.
  * Refused with WBC_ERR_STATE: wbc_update, wbc_solve, wbc_step_modes, wbc_step / wbc_cycle with
- * WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, and wbc_step with WBC_DUALS or WBC_DUALS_FORCE (no duals
- * instance reads the table yet). */
+ * WBC_SPLIT, WBC_FUSED or WBC_RESIDENT, and wbc_step with WBC_DUALS or WBC_DUALS_FORCE (neither
+ * flag's instance reads the table).  WBC_DUALS_TASK gives the 48 multipliers under the table
+ * (wbc_get_force_duals above). */
 int32_t wbc_set_force_task(wbc_engine* h, const double* table);
 /* Caller-owned device table [B][WBC_FT_LEN] (no copy, no host validation; 16-byte aligned; a caller may
  * rewrite it on the engine's stream every cycle, as a planner's forces are).  NULL restores the

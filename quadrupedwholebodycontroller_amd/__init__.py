@@ -19,7 +19,8 @@ behind the C-ABI in include/wbc.h.  This package is the Python view of that C-AB
                   contact-mode hypotheses (set_modes / step_modes) with each hypothesis' QP objective and the
                   best feasible one per state: flags OBJECTIVE / BEST, Engine.objective / best_modes;
                   which constraints bind: flag DUALS on step, Engine.duals / device_duals, dual_rows; under
-                  force bounds flag DUALS_FORCE, Engine.force_duals / device_force_duals (48 per robot)
+                  force bounds flag DUALS_FORCE, Engine.force_duals / device_force_duals (48 per robot), under a
+                  force task flag DUALS_TASK (the same 48, the same getters)
   Planner         batched motion planner (WbcReferenceMsg producer), see _capi.py
   workloads       synthetic inputs of the BASELINE.json configurations
   sharding        robot shards and the per-step all-gather of the multi-GPU path
@@ -30,7 +31,7 @@ libwbc_controller.so), as the reference's class is.
 
 The product path has no CPU fallback: without libwbc_hip.so or a GPU it raises.
 """
-from ._capi import (BEST, COLD, DEBUG, DUALS, DUALS_FORCE, DUAL_FORCE_LEN, FUSED, GROUP, NO_X, OBJECTIVE, RESIDENT, SPLIT, STATELESS, TIMED, QP_INFEASIBLE, QP_MAX_ITER, QP_NUMERIC, QP_OK, Engine, WbcError,  # noqa: F401
+from ._capi import (BEST, COLD, DEBUG, DUALS, DUALS_FORCE, DUALS_TASK, DUAL_FORCE_LEN, FUSED, GROUP, NO_X, OBJECTIVE, RESIDENT, SPLIT, STATELESS, TIMED, QP_INFEASIBLE, QP_MAX_ITER, QP_NUMERIC, QP_OK, Engine, WbcError,  # noqa: F401
                     WbcModel, WbcParams, anymal_model, default_params, load_library, model_from_urdf, split_debug, Planner,
                     WbcPlannerParams, ROBOT_PARAM_NAMES, robot_param_table, contact_normal_table,
                     base_body_row, base_body_table, base_body_with_payload, dual_rows, limits_row, limits_table,
@@ -38,7 +39,7 @@ from ._capi import (BEST, COLD, DEBUG, DUALS, DUALS_FORCE, DUAL_FORCE_LEN, FUSED
                     force_task_row, force_task_table)
 
 __all__ = ["Engine", "Planner", "WbcPlannerParams", "model_from_urdf", "WbcError", "WbcModel", "WbcParams", "anymal_model", "default_params", "load_library",
-           "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "OBJECTIVE", "BEST", "DUALS", "DUALS_FORCE", "DUAL_FORCE_LEN", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC",
+           "split_debug", "STATELESS", "DEBUG", "NO_X", "SPLIT", "TIMED", "COLD", "FUSED", "GROUP", "RESIDENT", "OBJECTIVE", "BEST", "DUALS", "DUALS_FORCE", "DUALS_TASK", "DUAL_FORCE_LEN", "QP_OK", "QP_MAX_ITER", "QP_INFEASIBLE", "QP_NUMERIC",
            "ROBOT_PARAM_NAMES", "robot_param_table", "contact_normal_table",
            "base_body_row", "base_body_table", "base_body_with_payload", "dual_rows", "limits_row", "limits_table",
            "force_bounds_row", "force_bounds_table", "force_task_row", "force_task_table"]

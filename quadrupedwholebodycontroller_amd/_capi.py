@@ -23,6 +23,8 @@ DUALS = 2048
 DUAL_LEN = 40  # WBC_DUAL_LEN: rows 4 leg + face, then 16 + 2 joint + side (side 0: tau >= -max, side 1: tau <= +max)
 # wbc_step only (default form), implies DUALS: the 40 and the multipliers of the per-foot normal-force bounds
 DUALS_FORCE = 4096
+# wbc_step only (default form), implies DUALS_FORCE: the same 48 under a per-robot force task (with or without one in force)
+DUALS_TASK = 8192
 DUAL_FORCE_LEN = 48  # WBC_DUAL_FORCE_LEN: the 40 rows, then 40 + 2 leg + side (side 0: n.f >= fn_min, side 1: n.f <= fn_max)
 QP_OK, QP_MAX_ITER, QP_INFEASIBLE, QP_NUMERIC = 0, 1, 2, 3
 # columns of the per-robot parameter table (WBC_RP_* in include/wbc.h; rows of RP_LEN doubles, the last reserved)
@@ -799,7 +801,9 @@ class Engine:
         return p.value
 
     def force_duals(self) -> np.ndarray:
-        """wbc_get_force_duals: (B, 48) multipliers after step(... | DUALS_FORCE): the 40 of duals(), then the
+        """wbc_get_force_duals: (B, 48) multipliers after step(... | DUALS_FORCE) or step(... | DUALS_TASK) (the
+        flag under a force task: the multipliers of the QP with the task's H and g, which grow with its weight
+        w, numbered alike): the 40 of duals(), then the
         per-foot normal-force bounds' (rows 40 + 2 leg + side: side 0 n.f >= fn_min, side 1 n.f <= fn_max); 0 for
         a row that does not exist or does not bind, all 0 where status is not QP_OK.  dual_rows() reshapes them."""
         d = np.zeros((self.batch, DUAL_FORCE_LEN))

@@ -57,6 +57,10 @@ extern "C" hipError_t wbc_launch_update_solve_lmd1(const wbc::KernelArgs* a, hip
 // KernelArgs::dual as [B][WBC_DUAL_FORCE_LEN])
 extern "C" hipError_t wbc_launch_update_solve_fnd0(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_update_solve_fnd1(const wbc::KernelArgs* a, hipStream_t st);
+// and the force-task units' duals instances (wbc_kernel_ftd0.hip, wbc_kernel_ftd1.hip: wbc_step with WBC_DUALS_TASK,
+// the same [B][WBC_DUAL_FORCE_LEN] under KernelArgs::ft)
+extern "C" hipError_t wbc_launch_update_solve_ftd0(const wbc::KernelArgs* a, hipStream_t st);
+extern "C" hipError_t wbc_launch_update_solve_ftd1(const wbc::KernelArgs* a, hipStream_t st);
 extern "C" hipError_t wbc_launch_reset(double* hist, const uint8_t* mask, int batch, hipStream_t st);
 extern "C" hipError_t wbc_launch_qmap(const uint8_t* masks, int batch, int32_t* map, hipStream_t st);
 extern "C" hipError_t wbc_preload_resident();
@@ -156,10 +160,13 @@ struct wbc_engine {
     // differ), allocated at the first step that carries that flag; without a force-bound table in force its step
     // reads d_fn_none: (-inf x 4, +inf x 4) in B rows (built at the first use).  step_duals: what the last wbc_step
     // wrote, which the four getters consult
+    // wbc_step with WBC_DUALS_TASK: d_dual48 again (DUALS_48); without a force-task table in force its step reads
+    // d_ft_plain: (0 x 12, 1, 0) in B rows (built at the first use)
     double* d_dual = nullptr;
     double* d_bb_def = nullptr;
     double* d_dual48 = nullptr;
     double* d_fn_none = nullptr;
+    double* d_ft_plain = nullptr;
     enum StepDuals { DUALS_NONE, DUALS_40, DUALS_48 };
     StepDuals step_duals = DUALS_NONE;
     // per-robot torque bounds and per-foot friction (KernelArgs::lm, [B][WBC_LM_LEN]; without: -+max_torque
@@ -503,6 +510,11 @@ int32_t refuse_force_duals_flag(const char* call, uint32_t flags) {
     if (!(flags & WBC_DUALS_FORCE)) return WBC_OK;
     return fail(WBC_ERR_ARG, std::string(call) + ": WBC_DUALS_FORCE is a flag of the default wbc_step");
 }
+// and so does WBC_DUALS_TASK (after every other check of the call)
+int32_t refuse_task_duals_flag(const char* call, uint32_t flags) {
+    if (!(flags & WBC_DUALS_TASK)) return WBC_OK;
+    return fail(WBC_ERR_ARG, std::string(call) + ": WBC_DUALS_TASK is a flag of the default wbc_step");
+}
 }  // namespace
 
 extern "C" {
@@ -645,7 +657,7 @@ int32_t wbc_destroy(wbc_engine* h) {
     void* ptrs[] = {h->d_model, h->d_params, h->d_limg, h->d_inblk, h->d_outblk, h->d_mask, h->d_modes, h->d_hist, h->d_work,
                     h->d_fb, h->d_dbg, h->d_qmap, h->rp.own, h->cn.own, h->d_rp_uni, h->bb.own, h->d_cn_flat,
                     h->d_obj, h->d_best, h->d_best_obj, h->d_best_tau, h->d_best_grf, h->d_dual, h->d_bb_def, h->lm.own, h->fn.own,
-                    h->d_dual48, h->d_fn_none, h->ft.own};
+                    h->d_dual48, h->d_fn_none, h->ft.own, h->d_ft_plain};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_in) (void)hipHostFree(h->h_in);
@@ -979,6 +991,8 @@ static int32_t ensure_ft_tables(wbc_engine* h) {
     return ensure_fn_none(h);
 }
 static const double kPlainForceTask[WBC_FT_LEN] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+// the plain-task rows a WBC_DUALS_TASK step reads when no force-task table is in force
+static int32_t ensure_ft_plain(wbc_engine* h) { return ensure_uniform(h, &h->d_ft_plain, kPlainForceTask, WBC_FT_LEN, "d_ft_plain"); }
 int32_t wbc_set_force_task(wbc_engine* h, const double* table) {
     return table_set(h, &wbc_engine::ft, table, "wbc_set_force_task", "d_ft", ft_row_error, ensure_ft_tables);
 }
@@ -1015,6 +1029,7 @@ int32_t wbc_update(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_mode_out_flags("wbc_update", flags)) return rc;
     if (const int32_t rc = refuse_duals_flag("wbc_update", flags)) return rc;
     if (const int32_t rc = refuse_force_duals_flag("wbc_update", flags)) return rc;
+    if (const int32_t rc = refuse_task_duals_flag("wbc_update", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     begin_update(h, a);
@@ -1032,6 +1047,7 @@ int32_t wbc_solve(wbc_engine* h, uint32_t flags) {
     if (const int32_t rc = refuse_duals_flag("wbc_solve", flags)) return rc;
     if (!h->updated) return fail(WBC_ERR_STATE, "wbc_solve before wbc_update");
     if (const int32_t rc = refuse_force_duals_flag("wbc_solve", flags)) return rc;
+    if (const int32_t rc = refuse_task_duals_flag("wbc_solve", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     wbc::KernelArgs a = make_args(h, flags);
     WBC_HIP(launch_solves(h, a));
@@ -1047,8 +1063,11 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
     if (const int32_t rc = refuse_mode_out_flags("wbc_step", flags)) return rc;
     // WBC_DUALS_FORCE implies WBC_DUALS, whose bit is ignored beside it (as WBC_BEST implies WBC_OBJECTIVE): the 48-entry
     // form has kernels, a buffer and getters of its own, and WBC_DUALS alone keeps its refusal under force bounds
-    const bool dforce = (flags & WBC_DUALS_FORCE) != 0;
-    const bool duals = (flags & WBC_DUALS) != 0 && !dforce;
+    // WBC_DUALS_TASK implies WBC_DUALS_FORCE in the same way: the same 48 entries, buffer and getters from the force-task
+    // units' duals instances, with or without a force-task table; the two older flags keep their refusals under one
+    const bool dtask = (flags & WBC_DUALS_TASK) != 0;
+    const bool dforce = (flags & WBC_DUALS_FORCE) != 0 && !dtask;
+    const bool duals = (flags & WBC_DUALS) != 0 && !dforce && !dtask;
     if (duals && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
     if (duals && h->fn.in_force)
@@ -1060,24 +1079,30 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
                                        "with wbc_set_force_task(h, NULL))");
     if (dforce && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
         return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS_FORCE belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
+    if (dtask && (flags & (WBC_SPLIT | WBC_FUSED | WBC_RESIDENT)))
+        return fail(WBC_ERR_ARG, "wbc_step: WBC_DUALS_TASK belongs to the default form (not WBC_SPLIT / WBC_FUSED / WBC_RESIDENT)");
     h->step_duals = wbc_engine::DUALS_NONE;
-    if (duals || dforce) {  // the engine's own tables for the ones the caller has not set, and the buffer
+    if (duals || dforce || dtask) {  // the engine's own tables for the ones the caller has not set, and the buffer
         if (const int32_t rc = ensure_rp_cn_bb_uniform(h)) return rc;
     }
-    if (dforce && !h->fn.in_force) {
+    if ((dforce || dtask) && !h->fn.in_force) {
         if (const int32_t rc = ensure_fn_none(h)) return rc;
+    }
+    if (dtask && !h->ft.in_force) {
+        if (const int32_t rc = ensure_ft_plain(h)) return rc;
     }
     WBC_HIP(hipSetDevice(h->device));
     if (duals && !h->d_dual) WBC_HIP(dalloc(&h->d_dual, (size_t)h->batch * WBC_DUAL_LEN));
-    if (dforce && !h->d_dual48) WBC_HIP(dalloc(&h->d_dual48, (size_t)h->batch * WBC_DUAL_FORCE_LEN));
+    if ((dforce || dtask) && !h->d_dual48) WBC_HIP(dalloc(&h->d_dual48, (size_t)h->batch * WBC_DUAL_FORCE_LEN));
     wbc::KernelArgs a = make_args(h, flags, io.in, io.out);
-    if (duals || dforce) {
+    if (duals || dforce || dtask) {
         if (!a.rp) a.rp = h->d_rp_uni;
         if (!a.cn) a.cn = h->d_cn_flat;
         if (!a.bb) a.bb = h->d_bb_def;
-        a.dual = dforce ? h->d_dual48 : h->d_dual;
+        a.dual = duals ? h->d_dual : h->d_dual48;
     }
-    if (dforce && !a.fn) a.fn = h->d_fn_none;  // (a missing limits table stays a null KernelArgs::lm, as in fn0 / fn1)
+    if ((dforce || dtask) && !a.fn) a.fn = h->d_fn_none;  // (a missing limits table stays a null KernelArgs::lm, as in fn0 / fn1)
+    if (dtask && !a.ft) a.ft = h->d_ft_plain;
     const bool timed = (flags & WBC_TIMED) != 0;  // event packets cost a few us between kernels
     if (timed) WBC_HIP(hipEventRecord(h->ev0, h->stream));
     if (flags & WBC_SPLIT) {
@@ -1101,7 +1126,10 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         // WBC_DUALS: the duals instance of (stateful), whatever the tables and masks; under
         // a limits table the limits units' own
         // WBC_DUALS_FORCE: the force-bound units' duals instance, whatever the tables
-        if (dforce) {
+        // WBC_DUALS_TASK: the force-task units' duals instance, whatever the tables
+        if (dtask) {
+            WBC_HIP((a.stateful ? wbc_launch_update_solve_ftd1 : wbc_launch_update_solve_ftd0)(&a, h->stream));
+        } else if (dforce) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_fnd1 : wbc_launch_update_solve_fnd0)(&a, h->stream));
         } else if (duals && a.lm) {
             WBC_HIP((a.stateful ? wbc_launch_update_solve_lmd1 : wbc_launch_update_solve_lmd0)(&a, h->stream));
@@ -1117,7 +1145,7 @@ static int32_t step_on(wbc_engine* h, uint32_t flags, const StepIO& io) {
         h->timed = true;
     }
     h->updated = false;
-    h->step_duals = dforce ? wbc_engine::DUALS_48 : duals ? wbc_engine::DUALS_40 : wbc_engine::DUALS_NONE;
+    h->step_duals = (dforce || dtask) ? wbc_engine::DUALS_48 : duals ? wbc_engine::DUALS_40 : wbc_engine::DUALS_NONE;
     return WBC_OK;
 }
 
@@ -1159,6 +1187,7 @@ int32_t wbc_step_modes(wbc_engine* h, uint32_t flags) {
     if (flags & WBC_DEBUG) return fail(WBC_ERR_ARG, "wbc_step_modes: no debug records for hypotheses");
     if (const int32_t rc = refuse_duals_flag("wbc_step_modes", flags)) return rc;
     if (const int32_t rc = refuse_force_duals_flag("wbc_step_modes", flags)) return rc;
+    if (const int32_t rc = refuse_task_duals_flag("wbc_step_modes", flags)) return rc;
     const uint32_t mode_out = (flags & WBC_BEST) ? kModeOutFlags : (flags & WBC_OBJECTIVE);  // WBC_BEST implies WBC_OBJECTIVE
     if (mode_out && (flags & WBC_SPLIT))
         return fail(WBC_ERR_ARG, "wbc_step_modes: WBC_OBJECTIVE / WBC_BEST belong to the default form (not WBC_SPLIT)");
@@ -1323,6 +1352,7 @@ int32_t wbc_cycle(wbc_engine* h, const double* base_pose, const double* nu, cons
     if (const int32_t rc = refuse_mode_out_flags("wbc_cycle", flags)) return rc;
     if (const int32_t rc = refuse_duals_flag("wbc_cycle", flags)) return rc;
     if (const int32_t rc = refuse_force_duals_flag("wbc_cycle", flags)) return rc;
+    if (const int32_t rc = refuse_task_duals_flag("wbc_cycle", flags)) return rc;
     WBC_HIP(hipSetDevice(h->device));
     const size_t B = (size_t)h->batch;
     if (!h->h_in) {

@@ -11,7 +11,8 @@
 // argument LM (21): lm0 and lm1, and lmd0 and lmd1, the same with WBC_STEP_DUALS.
 // Two more hold the instances under per-foot normal-force bounds, a seventh template argument FN (22): fn0 and fn1,
 // and fnd0 and fnd1, the same with WBC_STEP_DUALS (23: 48 multipliers per robot).
-// Two more hold the instances under per-robot reference contact forces, an eighth template argument FT (24): ft0 and ft1.
+// Two more hold the instances under per-robot reference contact forces, an eighth template argument FT (24): ft0 and ft1,
+// and ftd0 and ftd1, the same with WBC_STEP_DUALS (25: the 48 multipliers under the task).
 // Such a unit names its launcher and its template arguments (WBC_STEP_LAUNCHER, WBC_STEP_INSTANCE).  wbc_kernel_modes.hip holds the mode
 // loop, wbc_modes_kernel, and wbc_kernel_resident.hip the two instances of the resident cycle,
 // wbc_resident_kernel, under macros of their own (WBC_MODES_TU, WBC_RESIDENT_TU).  This file's own
@@ -5108,7 +5109,7 @@ static_assert(sizeof(SolveLds) <= sizeof(UpdLds), "the drain reuses the update s
 // (One instance per calling kernel, TAG = fb_tag(kind, STF): a shared callee is allocated for the
 // larger of its callers' register budgets, which raised the default step's to 512 registers and its
 // scratch to 2.2 KB.  The values are part of the instances' symbol names.)
-enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18, FB_STEP_FND = 20, FB_STEP_FT = 22 };
+enum FbKind { FB_MODES_OBJ = 0, FB_MODES = 1, FB_STEP = 2, FB_RESIDENT = 4, FB_STEP_RP = 6, FB_STEP_CN = 10, FB_STEP_DU = 12, FB_STEP_LM = 14, FB_STEP_LMD = 16, FB_STEP_FN = 18, FB_STEP_FND = 20, FB_STEP_FT = 22, FB_STEP_FTD = 24 };
 constexpr int fb_tag(FbKind kind, int stf = 0) { return (int)kind + stf; }
 constexpr bool fb_reads_fn(int tag) { return tag >= FB_STEP_FN; }  // the force-bound instances (KernelArgs::fn), limits instances too
 constexpr bool fb_reads_ft(int tag) { return tag >= FB_STEP_FT; }  // the force-task instances (KernelArgs::ft), force-bound instances too
@@ -5116,9 +5117,11 @@ constexpr bool fb_reads_rp(int tag) { return tag >= FB_STEP_RP; }  // the per-ro
 constexpr bool fb_reads_cn(int tag) { return tag >= FB_STEP_CN; }  // the contact-normal instances
 constexpr bool fb_writes_obj(int tag) { return tag == FB_MODES_OBJ; }  // the mode loop's objective instance (KernelArgs::obj)
 // the duals instances (KernelArgs::dual), contact-normal instances too: du0 / du1, lmd0 / lmd1 under a limits table, and
-// fnd0 / fnd1, the force-bound instances' (48 entries per robot: solve_phase<.., DU, LM, FN>)
+// fnd0 / fnd1, the force-bound instances' (48 entries per robot: solve_phase<.., DU, LM, FN>), and ftd0 / ftd1, the
+// force-task instances' (the same 48 under KernelArgs::ft: solve_phase<.., DU, LM, FN, FT>)
 constexpr bool fb_writes_dual(int tag) {
-    return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN) || (tag >= FB_STEP_FND && tag < FB_STEP_FT);
+    return (tag >= FB_STEP_DU && tag < FB_STEP_LM) || (tag >= FB_STEP_LMD && tag < FB_STEP_FN) || (tag >= FB_STEP_FND && tag < FB_STEP_FT) ||
+           tag >= FB_STEP_FTD;
 }
 constexpr bool fb_reads_lm(int tag) { return tag >= FB_STEP_LM; }  // the limits instances (KernelArgs::lm), contact-normal instances too
 // The nine per-robot values of a table row (wbc.h WBC_RP_*) over the engine-wide ones; a row the step
@@ -5179,7 +5182,7 @@ __device__ __attribute__((noinline)) void drain_fallbacks(const KernelArgs* ka, 
 #pragma unroll
                 for (int c = 0; c < WBC_FT_LEN - 1; ++c) tv[c] = t[c];
                 f.ft = ft_bad_column(tv) >= 0 ? nullptr : ka->ft;
-                solve_general_qp<true, false, false, true, true, true>(f, q1, *L);
+                solve_general_qp<true, false, fb_writes_dual(TAG), true, true, true>(f, q1, *L);
             } else
             solve_general_qp<true, false, fb_writes_dual(TAG), true, true>(f, q1, *L);
         } else {
@@ -5250,12 +5253,13 @@ constexpr bool STEP_DU = false;
 // 24): each lane loads, with its inputs, its share of row qp of KernelArgs::ft, indexed as the other rows are:
 // lane i < 12 the reference force entry fref_i, every lane the weight w.  The two reductions put w on the
 // diagonal of a stance slot and subtract w fref_i from its gradient; solve16 and the pass are the force-bound
-// instances'.  A fallback callee of their own (FB_STEP_FT).
+// instances'.  A fallback callee of their own (FB_STEP_FT).  With WBC_STEP_DUALS (wbc_kernel_ftd0.hip,
+// wbc_kernel_ftd1.hip) they are the instances of a wbc_step with WBC_DUALS_TASK: the 48 multipliers of
+// the fnd instances under the task's H and g (solve16's DU under FN, unchanged: the task touches no row; FB_STEP_FTD).
 template <int STF, bool SONLY = false, bool RP = false, bool CN = false, bool BB = false, bool LM = false, bool FN = false,
           bool FT = false>
 WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     static_assert(!FT || FN, "the force-task instances are force-bound instances");
-    static_assert(!FT || !STEP_DU, "no duals instance reads the force task");
     static_assert(!FN || LM, "the force-bound instances are limits instances");
     static_assert(!CN || RP, "the contact-normal instances are per-robot-parameter instances");
     static_assert(!BB || CN, "the base-body instances are contact-normal instances");
@@ -5514,7 +5518,7 @@ WBC_UPDATE_KERNEL_ATTR void wbc_update_solve_kernel(KernelArgs a) {
     }
     const unsigned long long fm = __ballot(fb && lane == 0);
     if (fm)
-        drain_fallbacks<fb_tag(FT ? FB_STEP_FT : FN ? (STEP_DU ? FB_STEP_FND : FB_STEP_FN) : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
+        drain_fallbacks<fb_tag(FT ? (STEP_DU ? FB_STEP_FTD : FB_STEP_FT) : FN ? (STEP_DU ? FB_STEP_FND : FB_STEP_FN) : LM ? (STEP_DU ? FB_STEP_LMD : FB_STEP_LM) : STEP_DU ? FB_STEP_DU : CN ? FB_STEP_CN : RP ? FB_STEP_RP : FB_STEP, STF)>((const KernelArgs*)__builtin_amdgcn_kernarg_segment_ptr(), fm, qp,
                            reinterpret_cast<SolveLds*>(&L));
 #ifdef WBC_ISTAMPS
     if (lane_id() == 0) {

@@ -213,7 +213,8 @@ struct KernelArgs {
     // row qp for QP qp, in the hotstart's row numbering (wbc.h), zero where status is not WBC_QP_OK;
     // written only by the duals instances of the default step (wbc_kernel_du0.hip, wbc_kernel_du1.hip)
     // and their fallback solve.  For the force-bound duals instances (wbc_kernel_fnd0.hip, wbc_kernel_fnd1.hip:
-    // wbc_step with WBC_DUALS_FORCE) the same member points at a buffer of [batch][WBC_DUAL_FORCE_LEN]:
+    // wbc_step with WBC_DUALS_FORCE; and wbc_kernel_ftd0.hip, wbc_kernel_ftd1.hip: WBC_DUALS_TASK)
+    // the same member points at a buffer of [batch][WBC_DUAL_FORCE_LEN]:
     // the stride is a compile-time constant of the instance.  After obj, so that no other argument's offset moves.  (Keep the trailing
     // comment on the declaration's own line: tests/test_modes_objective_cpu.py scans for lines ending in ';'
     // and expects obj to be the last of them)
@@ -236,7 +237,8 @@ struct KernelArgs {
     const double* fn; /* [B][WBC_FN_LEN] */
     // Per-robot reference contact forces and their weight (wbc_set_force_task / wbc_bind_device_force_task):
     // [batch][WBC_FT_LEN], row qp for QP qp (fref[12], weight, one reserved; ft_bad_column below); read only by
-    // the force-task instances of the default step (wbc_kernel_ft0.hip, wbc_kernel_ft1.hip), which are instances
+    // the force-task instances of the default step (wbc_kernel_ft0.hip, wbc_kernel_ft1.hip, and their duals
+    // instances wbc_kernel_ftd0.hip, wbc_kernel_ftd1.hip), which are instances
     // of every other table too: the engine points fn, bb, cn and rp at tables of its own where none is in force,
     // and a null lm is taken as the force-bound instances take it.  Last, so that no other argument's offset
     // moves.  (The block comment stays behind the declaration, as lm's.)

@@ -1,5 +1,5 @@
 """What the step-timing tools share (cn_timing.py, bb_timing.py, duals_timing.py, lm_timing.py, fn_timing.py,
-ft_timing.py, modes_obj_timing.py): an engine on a stream, of this build or of another build's library; HIP events around
+ft_timing.py, ftd_timing.py, modes_obj_timing.py): an engine on a stream, of this build or of another build's library; HIP events around
 back-to-back steps, as bench.py times a step; the rotation of the forms over the rounds; the JSON line; and the
 numpy oracles' active-set passes.  Each tool keeps its forms, its ratios and its command line."""
 import json
